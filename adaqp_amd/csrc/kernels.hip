@@ -17,7 +17,7 @@
 //  * RNG is a stateless counter hash (triple32) of (seed, node, feature) —
 //    no curand state; bit-compatible with the CPU oracle in ops/quant.py.
 //  * spmm_csr: one SUB-wavefront per destination-row segment (hub rows are
-//    split and atomically combined), dtype-templated (fp32 / bf16 with fp32
+//    split; partial sums combined in fixed order), dtype-templated (fp32 / bf16 with fp32
 //    accumulate), vector width chosen so row-base loads stay aligned, fused
 //    src/dst degree scaling, XCD-aware block swizzle, int32 column indices
 //    + segment bounds (half the index bytes), four gather loads in flight.
@@ -227,8 +227,10 @@ __global__ void quant_unpack_kernel(
 // spmm_csr: y[r] = dst_scale[r] * sum_{e in row r} src_scale[c_e] * x[c_e]
 //
 // One SUB-wavefront (SW in {16,32,64}, chosen to cover F) per destination-row
-// SEGMENT (seg_* arrays; hub rows are split to <=SEG_EDGES edges and combined
-// with atomics into pre-zeroed rows). Lane sl owns features
+// SEGMENT (seg_* arrays; hub rows are split to <=SEG_EDGES edges; each such
+// segment stores its fp32 partial into its own slot of a scratch buffer and
+// combine_parts_kernel sums a row's slots in segment order, so the result
+// is bit-identical from run to run). Lane sl owns features
 // [VE*sl, VE*sl+VE) per chunk of VE*SW, VE picked host-side so the
 // VE*sizeof(T)-byte row-base loads stay aligned (VE | F). Two edges are
 // accumulated in flight (dual accumulators) to cover gather latency.
@@ -237,16 +239,25 @@ __global__ void quant_unpack_kernel(
 // each XCD a contiguous chunk of work items so clustered neighbor rows
 // hit the same L2 (guide §5.5 T1).
 // ---------------------------------------------------------------------------
+// One wavefront per split row: y[rows[j]] = sum of its partial slots
+// [part_ptr[j], part_ptr[j+1]) in slot order (an empty range writes zeros).
 template <typename T>
-__global__ void zero_rows_kernel(T* __restrict__ y,
-                                 const int32_t* __restrict__ rows,
-                                 int64_t n, int64_t F) {
+__global__ void combine_parts_kernel(T* __restrict__ y,
+                                     const float* __restrict__ part,
+                                     const int32_t* __restrict__ rows,
+                                     const int32_t* __restrict__ part_ptr,
+                                     int64_t n, int64_t F) {
     const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
                       + threadIdx.x / WAVE;
     if (wid >= n) return;
     T* p = y + (int64_t)rows[wid] * F;
-    for (int64_t f = threadIdx.x & (WAVE - 1); f < F; f += WAVE)
-        p[f] = T(0);
+    const int64_t p0 = part_ptr[wid], p1 = part_ptr[wid + 1];
+    for (int64_t f = threadIdx.x & (WAVE - 1); f < F; f += WAVE) {
+        float acc = 0.f;
+        for (int64_t q = p0; q < p1; ++q) acc += part[q * F + f];
+        if constexpr (sizeof(T) == 2) p[f] = f32_to_bf16(acc);
+        else p[f] = acc;
+    }
 }
 
 // VE = elements per lane per load; chosen host-side as the largest of
@@ -265,7 +276,8 @@ __global__ void spmm_csr_kernel(
     T* __restrict__ y,
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     const int32_t* __restrict__ seg_row, const int32_t* __restrict__ seg_e0,
-    const int32_t* __restrict__ seg_e1, const uint8_t* __restrict__ seg_multi,
+    const int32_t* __restrict__ seg_e1, const int32_t* __restrict__ seg_part,
+    float* __restrict__ part,
     int64_t n_seg, int64_t F, int64_t n_local) {
     constexpr bool BF = sizeof(T) == 2;
     constexpr int NB = VE * sizeof(T);
@@ -283,7 +295,7 @@ __global__ void spmm_csr_kernel(
     for (int64_t it = sub0; it < n_seg; it += stride) {
         const int64_t r = seg_row[it];
         const int64_t e0 = seg_e0[it], e1 = seg_e1[it];
-        const bool multi = seg_multi[it];
+        const int64_t slot = seg_part[it];     // >= 0: row split across segments
         const float ds = dst_scale ? dst_scale[r] : 1.f;
         for (int64_t f0 = (int64_t)sl * VE; f0 < F; f0 += (int64_t)SW * VE) {
             float acc0[VE], acc1[VE];
@@ -348,7 +360,7 @@ __global__ void spmm_csr_kernel(
                     acc0[k] = fmaf(to_f32<T>(v[k]), s, acc0[k]);
             }
             T* yr = y + r * F + f0;
-            if (!multi) {
+            if (slot < 0) {
                 T outv[VE];
 #pragma unroll
                 for (int k = 0; k < VE; ++k) {
@@ -357,20 +369,13 @@ __global__ void spmm_csr_kernel(
                     else outv[k] = o;
                 }
                 *reinterpret_cast<Raw*>(yr) = *reinterpret_cast<const Raw*>(outv);
-            } else if constexpr (BF) {
-                // long row split across segments: combine via packed atomics
-#pragma unroll
-                for (int k = 0; k < VE; k += 2) {
-                    __hip_bfloat162 v;
-                    v.x = __float2bfloat16((acc0[k] + acc1[k]) * ds);
-                    v.y = __float2bfloat16((acc0[k + 1] + acc1[k + 1]) * ds);
-                    unsafeAtomicAdd(reinterpret_cast<__hip_bfloat162*>(yr + k), v);
-                }
             } else {
+                // long row split across segments: fp32 partial into this
+                // segment's own slot, summed by combine_parts_kernel
+                float* pp = part + slot * F + f0;
 #pragma unroll
                 for (int k = 0; k < VE; ++k)
-                    atomicAdd(reinterpret_cast<float*>(yr) + k,
-                              (acc0[k] + acc1[k]) * ds);
+                    pp[k] = (acc0[k] + acc1[k]) * ds;
             }
         }
     }
@@ -538,7 +543,8 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
               torch::Tensor xr, torch::Tensor y, torch::Tensor src_scale,
               torch::Tensor dst_scale, torch::Tensor seg_row,
               torch::Tensor seg_e0, torch::Tensor seg_e1,
-              torch::Tensor seg_multi, torch::Tensor zero_rows) {
+              torch::Tensor seg_part, torch::Tensor zero_rows,
+              torch::Tensor part_ptr, int64_t n_part) {
     CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
     const bool bf16 = xl.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(bf16 || xl.scalar_type() == torch::kFloat32,
@@ -555,22 +561,36 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
         xr_ptr = xr.data_ptr();
     }
     auto s = cur_stream();
-    if (zero_rows.numel()) {
+    TORCH_CHECK(seg_part.scalar_type() == torch::kInt32 &&
+                seg_part.numel() == n_seg &&
+                zero_rows.scalar_type() == torch::kInt32 &&
+                part_ptr.scalar_type() == torch::kInt32 &&
+                part_ptr.numel() == zero_rows.numel() + 1,
+                "seg_part/zero_rows/part_ptr must be the int32 arrays "
+                "SpmmView builds");
+    // one fp32 [F] slot per segment of a split row (SpmmView.n_part of them)
+    TORCH_CHECK(n_part >= 0 && n_part <= n_seg, "bad partial slot count");
+    torch::Tensor part = torch::empty(
+        {n_part, F}, xl.options().dtype(torch::kFloat32));
+    auto combine = [&]() {
+        if (!zero_rows.numel()) return;
         const dim3 zb(256), zg((zero_rows.numel() + 3) / 4);
         if (bf16)
-            zero_rows_kernel<ushort><<<zg, zb, 0, s>>>(
+            combine_parts_kernel<ushort><<<zg, zb, 0, s>>>(
                 reinterpret_cast<ushort*>(y.data_ptr()),
-                zero_rows.data_ptr<int32_t>(), zero_rows.numel(), F);
+                part.data_ptr<float>(), zero_rows.data_ptr<int32_t>(),
+                part_ptr.data_ptr<int32_t>(), zero_rows.numel(), F);
         else
-            zero_rows_kernel<float><<<zg, zb, 0, s>>>(
-                y.data_ptr<float>(), zero_rows.data_ptr<int32_t>(),
+            combine_parts_kernel<float><<<zg, zb, 0, s>>>(
+                y.data_ptr<float>(), part.data_ptr<float>(),
+                zero_rows.data_ptr<int32_t>(), part_ptr.data_ptr<int32_t>(),
                 zero_rows.numel(), F);
-    }
-    if (n_seg == 0) return;
+    };
+    if (n_seg == 0) { combine(); return; }
     // largest vector width dividing F (keeps every row-base load aligned)
     int ve = bf16 ? 8 : 4;
     while (ve > 1 && F % ve) ve >>= 1;
-    if (bf16 && ve == 1) ve = 2;              // bf16 atomics need even lanes
+    if (bf16 && ve == 1) ve = 2;              // bf16 loads are >= one dword
     TORCH_CHECK(!bf16 || F % 2 == 0, "bf16 spmm needs even feature dim");
     // sub-wavefront width: smallest of {16,32,64} covering F with ve/lane
     int sw = 16;
@@ -591,7 +611,7 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
                 "seg_e0/e1 must be int32 (SpmmView builds them)");
     const int32_t* e0_p = seg_e0.data_ptr<int32_t>();
     const int32_t* e1_p = seg_e1.data_ptr<int32_t>();
-    const uint8_t* sm_p = seg_multi.data_ptr<uint8_t>();
+    const int32_t* sp_p = seg_part.data_ptr<int32_t>();
     auto run = [&](auto sw_tag, auto t_tag, auto ve_tag) {
         constexpr int SWC = decltype(sw_tag)::value;
         using TC = typename decltype(t_tag)::type;
@@ -600,7 +620,7 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
             ind_p, reinterpret_cast<const TC*>(xl.data_ptr()),
             reinterpret_cast<const TC*>(xr_ptr),
             reinterpret_cast<TC*>(y.data_ptr()), ss_p, ds_p,
-            sr_p, e0_p, e1_p, sm_p, n_seg, F, n_local);
+            sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(), n_seg, F, n_local);
     };
     struct FT { using type = float; };
     struct BT { using type = ushort; };
@@ -624,6 +644,7 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
         case 32: by_ve(std::integral_constant<int,32>{}); break;
         default: by_ve(std::integral_constant<int,16>{}); break;
     }
+    combine();
 }
 
 

@@ -123,16 +123,19 @@ class SpmmView:
 
     Power-law graphs put 10^4-10^5 edges on hub rows; a single
     sub-wavefront grinding one such row serially becomes the kernel's
-    critical path. Rows are split into <=SEG_EDGES-edge segments; rows
-    with >1 segment combine via global atomics into pre-zeroed output
-    rows (SURVEY.md §7 'hard parts': row-binning / load imbalance).
+    critical path. Rows are split into <=SEG_EDGES-edge segments; each
+    segment of a row with >1 segment writes its partial sum to its own
+    slot (``seg_part``) and a second pass adds a row's slots
+    (``part_ptr``, one range per ``zero_rows`` entry) in segment order,
+    so results are bit-identical from run to run (SURVEY.md §7 'hard
+    parts': row-binning / load imbalance).
 
     ``col_block`` > 0 additionally PERMUTES the edge array into
     column-block-major order (segments keyed by (col/col_block, row)):
     the grid sweeps one x column block at a time, so the block stays
     LLC-resident while every consumer reads it — same kernel, different
-    work-item layout. Costs atomic combines for every row spanning >1
-    block.
+    work-item layout. Costs a partial-sum combine for every row spanning
+    >1 block.
     """
 
     def __init__(self, indptr: Tensor, indices: Tensor, base: int, nrows: int,
@@ -189,6 +192,20 @@ class SpmmView:
             self.seg_e1 = e1
             self.seg_multi = multi_mask[seg_row].to(torch.uint8)
             self.zero_rows = torch.nonzero(multi_mask, as_tuple=True)[0].to(torch.int32)
+        # partial-sum slots: a split row's segments get consecutive slots
+        # in segment order; part_ptr[j]:part_ptr[j+1] is zero_rows[j]'s range
+        multi_seg = torch.nonzero(self.seg_multi, as_tuple=True)[0]
+        multi_row = self.seg_row[multi_seg].to(torch.int64)
+        order = torch.argsort(multi_row, stable=True)
+        slot = torch.empty_like(order)
+        slot[order] = torch.arange(order.numel(), dtype=torch.int64)
+        seg_part = torch.full((self.seg_row.numel(),), -1, dtype=torch.int64)
+        seg_part[multi_seg] = slot
+        cnt = torch.bincount(multi_row, minlength=nrows)[self.zero_rows.to(torch.int64)]
+        self.seg_part = seg_part.to(torch.int32)
+        self.part_ptr = torch.cat([torch.zeros(1, dtype=torch.int64),
+                                   torch.cumsum(cnt, 0)]).to(torch.int32)
+        self.n_part = int(multi_seg.numel())
         # int32 column indices + segment bounds: halves the kernel's
         # index-read bytes (~1 GB -> 0.5 GB per pass on full products);
         # node/edge counts are always < 2^31
@@ -198,7 +215,9 @@ class SpmmView:
         self._on = None
 
     def to(self, device):
-        for n in ('indices', 'seg_row', 'seg_e0', 'seg_e1', 'seg_multi', 'zero_rows'):
+        # seg_multi stays on the host: only the slot construction reads it
+        for n in ('indices', 'seg_row', 'seg_e0', 'seg_e1', 'zero_rows',
+                  'seg_part', 'part_ptr'):
             setattr(self, n, getattr(self, n).to(device))
         return self
 
@@ -232,7 +251,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
                           src_scale if src_scale is not None else empty,
                           dst_scale if dst_scale is not None else empty,
                           view.seg_row, view.seg_e0, view.seg_e1,
-                          view.seg_multi, view.zero_rows)
+                          view.seg_part, view.zero_rows, view.part_ptr,
+                          view.n_part)
         return out
     x = (torch.cat([x_local, x_remote], dim=0)
          if x_remote is not None and x_remote.numel() else x_local)

@@ -11,6 +11,10 @@ Metric (BASELINE.json): per-epoch time (s), ogbn-products GraphSAGE
 8-part, on a synthetic graph of that shape (no network for datasets)
 with random-init weights. Strong scaling: the global graph is fixed;
 N ranks = N partitions.
+
+A plain run does only what the headline figure needs: setup, warmup,
+the K timed epochs, the optional ``--dump-outputs`` and the result line.
+``--full`` adds the post-run accuracy evaluation (``config.test_acc``).
 """
 import argparse
 import json
@@ -55,6 +59,16 @@ def parse_args():
     p.add_argument('--dtype', type=str, default='fp32', choices=['fp32', 'bf16'],
                    help='compute dtype (fp32 matches the reference; bf16 '
                         'halves activation traffic, fp32 master weights)')
+    p.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                   help='after the timed epochs, write what the last timed '
+                        'epoch computed (loss, a fixed seeded row sample of '
+                        'the logits, reduced gradients, updated weights) as '
+                        'DIR/<name>.npy; with N>1 ranks loss and logits are '
+                        'per rank (<name>_rank<r>.npy) and the 64 MB budget '
+                        'is shared')
+    p.add_argument('--full', action='store_true',
+                   help='also run the checks a plain timing run skips: the '
+                        'train/val/test evaluation that fills config.test_acc')
     return p.parse_args()
 
 
@@ -69,6 +83,18 @@ def get_dist_env(args):
     os.environ.setdefault('WORLD_SIZE', '1')
     os.environ.setdefault('LOCAL_RANK', str(rank))
     return rank, world
+
+
+def _set_deterministic(mode, warn_only):
+    """torch.use_deterministic_algorithms, minus its import of the whole
+    compiler stack (torch._inductor/_dynamo: 1.56 s of a ~20 s setup in a
+    host profile of this script) where the underlying setter is exposed;
+    the public call is the fallback."""
+    setter = getattr(torch._C, '_set_deterministic_algorithms', None)
+    try:
+        setter(mode, warn_only=warn_only)
+    except TypeError:       # setter absent or its signature changed
+        torch.use_deterministic_algorithms(mode, warn_only=warn_only)
 
 
 def prepare_partition(args, rank, world):
@@ -89,7 +115,16 @@ def prepare_partition(args, rank, world):
     # driver's strong-scaling curve divides times for the SAME problem.
     # Contiguous range splits for world in {1,2,4,8} align with the
     # planted 8-range boundaries.
-    g = synth_graph(args.dataset, 8, seed=17, scale=args.scale)
+    # the generator's teacher labels scatter-add on the GPU; the
+    # deterministic variant keeps the inputs bit-identical from run to run
+    # (float atomics could otherwise flip a near-tied argmax label)
+    det = torch.are_deterministic_algorithms_enabled()
+    det_warn = torch.is_deterministic_algorithms_warn_only_enabled()
+    _set_deterministic(True, True)
+    try:
+        g = synth_graph(args.dataset, 8, seed=17, scale=args.scale)
+    finally:
+        _set_deterministic(det, det_warn)
     assign = range_assignment(g.num_nodes, world)
     in_deg, out_deg = global_degrees(g)
     lg = build_local_graph(g, assign, rank, world, in_deg, out_deg)
@@ -97,6 +132,43 @@ def prepare_partition(args, rank, world):
         print(f'# partition prep {time.time()-t0:.1f}s: '
               f'{g.num_nodes} nodes {g.num_edges} edges', file=sys.stderr)
     return lg
+
+
+# logits are [num_nodes, num_classes] (~460 MB at full scale): dump a fixed
+# seeded sample of rows (split evenly over the ranks), which with one copy
+# of the weights and gradients stays well inside the 64 MB budget
+DUMP_LOGIT_ROWS = 65536
+
+
+def dump_outputs(out_dir, rank, world, loss, logits, model):
+    """Write the last timed epoch's results — the loss train_epoch
+    returned, the logits it computed, and the gradients/weights it left
+    on the model — as float32/float64 .npy files. Every rank writes its
+    loss and logits sample; weights and reduced gradients are the same on
+    all ranks, so rank 0 alone writes them."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f'_rank{rank}' if world > 1 else ''
+
+    def save(name, t, dtype, sfx=sfx):
+        np.save(os.path.join(out_dir, f'{name}{sfx}.npy'),
+                t.detach().to('cpu', dtype).numpy())
+
+    save('loss', loss.reshape(1), torch.float64)
+    n = logits.shape[0]
+    keep = max(DUMP_LOGIT_ROWS // world, 1)
+    if n > keep:
+        gen = torch.Generator().manual_seed(2024)
+        rows = torch.randperm(n, generator=gen)[:keep].sort().values
+        logits = logits[rows.to(logits.device)]
+    save('logits', logits, torch.float32)
+    if rank != 0:
+        return
+    for pname, p in model.named_parameters():
+        tag = pname.replace('.', '_')
+        save(f'param_{tag}', p, torch.float32, sfx='')
+        if p.grad is not None:
+            save(f'grad_{tag}', p.grad, torch.float32, sfx='')
 
 
 def main():
@@ -150,19 +222,30 @@ def main():
         if use_gpu:
             torch.cuda.synchronize()
 
+    last = {}
+    if args.dump_outputs:
+        # keep a handle on the newest forward's logits (no copy, no sync)
+        model.register_forward_hook(
+            lambda mod, inp, out: last.__setitem__('logits', out))
+
+    loss = None
     for _ in range(args.warmup):
         train_epoch(engine, model, opt, gc, multilabel)
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        train_epoch(engine, model, opt, gc, multilabel)
+        loss = train_epoch(engine, model, opt, gc, multilabel)
     sync()
     elapsed = torch.tensor([time.perf_counter() - t0],
                            device=comm.device if use_gpu else 'cpu')
     comm.all_reduce_max(elapsed)
     per_epoch = float(elapsed.item()) / args.steps
 
-    metrics = evaluate(engine, model, multilabel)
+    if args.dump_outputs and loss is not None:
+        dump_outputs(args.dump_outputs, rank, world, loss, last['logits'],
+                     model)
+
+    test_acc = evaluate(engine, model, multilabel)['test'] if args.full else None
 
     if rank == 0:
         n, e, _, _, _ = DATASET_SHAPES[args.dataset]
@@ -193,7 +276,7 @@ def main():
                 'global_batch': 'full-graph',
                 'seq_len': None,
                 'parallelism': f'graph-partition dp{world}',
-                'test_acc': metrics['test'],
+                'test_acc': test_acc,
             },
         }
         print(json.dumps(out))

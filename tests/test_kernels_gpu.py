@@ -116,7 +116,7 @@ def test_spmm_matches_torch(F):
 
 
 def test_spmm_long_row_segmentation():
-    """A hub row longer than SEG_EDGES must be split and atomically
+    """A hub row longer than SEG_EDGES must be split and its partial sums
     combined; result must still match the dense reference."""
     from adaqp_amd.ops.kernels import SpmmView, spmm, SEG_EDGES
     _native()
@@ -139,6 +139,45 @@ def test_spmm_long_row_segmentation():
             A[r, c] += 1
     ref = A @ x.cpu()
     assert torch.allclose(y.cpu(), ref, atol=1e-2, rtol=1e-4)
+
+
+@pytest.mark.parametrize('col_block', [0, 64])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+def test_spmm_split_rows_bit_reproducible(dtype, col_block):
+    """Rows split across segments (several hubs, an empty row, more
+    segments than one block holds) are combined in a fixed order: repeated
+    calls give bit-identical results, and fp32 matches the dense reference
+    (same bound as test_spmm_long_row_segmentation: ~800 fp32 terms)."""
+    from adaqp_amd.ops.kernels import SpmmView, spmm, SEG_EDGES
+    _native()
+    gen = torch.Generator().manual_seed(11)
+    N, F, R = 300, 136, 70            # F: no multiple of the 64x4 lane tile
+    degs = [3 * SEG_EDGES + 17, 0, 2 * SEG_EDGES, SEG_EDGES + 1, SEG_EDGES] + \
+        torch.randint(1, 9, (R - 5,), generator=gen).tolist()
+    indptr = torch.zeros(R + 1, dtype=torch.int64)
+    indptr[1:] = torch.cumsum(torch.tensor(degs), 0)
+    indices = torch.randint(0, N, (int(indptr[-1]),), generator=gen)
+    x = torch.randn(N, F, generator=gen).to('cuda', dtype)
+    view = SpmmView(indptr.cuda(), indices.cuda(), 0, R,
+                    col_block=col_block).to('cuda')
+    assert view.n_part >= 3 + 2 + 2
+    assert int(view.part_ptr[-1]) == view.n_part
+    assert int(view.seg_part.max()) == view.n_part - 1
+    y0 = spmm(view, x, None, None, None).clone()
+    for _ in range(3):
+        assert torch.equal(spmm(view, x, None, None, None), y0)
+    assert torch.equal(y0[1], torch.zeros(F, device='cuda', dtype=dtype))
+    A = torch.zeros(R, N)
+    A.index_put_((torch.repeat_interleave(torch.arange(R),
+                                          torch.tensor(degs)), indices),
+                 torch.ones(indices.numel()), accumulate=True)
+    ref = A @ x.float().cpu()          # exact inputs, fp32 accumulate
+    if dtype == torch.float32:
+        assert torch.allclose(y0.cpu(), ref, atol=1e-2, rtol=1e-4)
+    else:
+        # fp32 accumulate, ONE rounding to bf16 (8 significand bits: half
+        # an ulp is 2^-9 relative) on top of the fp32 bound above
+        assert torch.allclose(y0.float().cpu(), ref, atol=1e-2, rtol=2 ** -8)
 
 
 def test_spmm_empty_rows():

@@ -18,6 +18,26 @@ def _random_csr(rows, max_deg, seed, hub=None):
     return indptr, indices
 
 
+def test_partial_slots_partition_split_rows():
+    """Every segment of a split row owns exactly one partial-sum slot, a
+    row's slots are the contiguous range part_ptr names for it, in segment
+    order, and unsplit segments own none — in both work-item layouts."""
+    rows = 120
+    indptr, indices = _random_csr(rows, 30, 5, hub=4 * SEG_EDGES + 9)
+    for cb in (0, 16):
+        v = SpmmView(indptr, indices, 0, rows, col_block=cb)
+        assert v.n_part >= 5 and int(v.part_ptr[0]) == 0
+        assert int(v.part_ptr[-1]) == v.n_part
+        assert v.part_ptr.numel() == v.zero_rows.numel() + 1
+        assert ((v.seg_part >= 0) == v.seg_multi.bool()).all()
+        used = v.seg_part[v.seg_part >= 0]
+        assert sorted(used.tolist()) == list(range(v.n_part))
+        for j, r in enumerate(v.zero_rows.tolist()):
+            mine = v.seg_part[(v.seg_row == r) & (v.seg_part >= 0)].tolist()
+            assert mine == list(range(int(v.part_ptr[j]),
+                                      int(v.part_ptr[j + 1])))
+
+
 def test_segments_cover_all_edges_exactly():
     for seed in range(3):
         rows = 200
