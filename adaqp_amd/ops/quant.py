@@ -16,11 +16,14 @@ oracle):
   Each node occupies ceil(F*bits/8) bytes.
 - RNG: stateless counter hash of (seed, node_tag, feature) — no curand
   state; the SAME noise sequence on CPU/HIP, so packings are statistically
-  identical and byte-identical except where FP contraction (FMA) on the
-  GPU lands a value exactly on a rounding boundary (< 0.5% of bytes in
-  tests/test_kernels_gpu.py). Harmless: only the sender's kernel ever
-  produces a given payload, so there is no cross-device mismatch on the
-  wire.
+  identical and byte-identical except where the fp32 evaluation of
+  (x - rmin)*scale + u (with or without FMA contraction) lands within
+  4 * 2^-24 * (2^bits + 1) of an integer: only there may a level differ,
+  by exactly one, towards that boundary. The tests enforce this against a
+  float64 oracle (tests/kernel_oracles.py::check_packed); every other
+  level, the bf16 params and the pad bits must match exactly. Harmless:
+  only the sender's kernel ever produces a given payload, so there is no
+  cross-device mismatch on the wire.
 - scale is rounded to bf16 BEFORE quantizing, so the receiver's bf16
   dequant is the exact inverse (the reference quantizes with the fp32
   scale but ships bf16 — a small bias it tolerates).
