@@ -30,43 +30,11 @@
 
 #include <cstdint>
 
-#define WAVE 64
 #define CHECK_DEV(x) TORCH_CHECK(x.is_cuda(), #x " must be on the GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
 
-// ---------------------------------------------------------------------------
-// RNG: triple32 hash -> U[0,1). Must match ops/quant.py::_hash_u32 exactly.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t hash_u32(uint32_t h) {
-    h ^= h >> 16; h *= 0x7FEB352Du;
-    h ^= h >> 15; h *= 0x846CA68Bu;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ float uniform01(uint32_t seed, uint32_t tag, uint32_t feat) {
-    uint32_t h = seed ^ (tag * 0x9E3779B9u) ^ (feat * 0x85EBCA6Bu);
-    return (float)((double)hash_u32(h) * 2.3283064365386963e-10);
-}
-
-// round-to-nearest-even f32 -> bf16 bits (parity with torch .to(bfloat16))
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-    uint32_t b = __float_as_uint(f);
-    uint32_t r = (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
-    return (uint16_t)r;
-}
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) {
-    return __uint_as_float(((uint32_t)h) << 16);
-}
-
-// T = float (V=4 feats/lane) or ushort bf16 bits (V=8 feats/lane); fp32 accumulate.
-template <typename T>
-__device__ __forceinline__ float to_f32(T v);
-template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f32<ushort>(ushort v) {
-    return bf16_to_f32(v);
-}
-
+// hash_u32 / uniform01 / f32_to_bf16 / bf16_to_f32 / to_f32 and WAVE
+#include "device_common.h"
 
 // ---------------------------------------------------------------------------
 // quant_pack: one wave per node.
@@ -648,6 +616,19 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
 }
 
 
+// norm_act.hip
+void norm_act_fwd(torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+                  double eps, double p, int64_t seed, bool training,
+                  torch::Tensor y, torch::Tensor mean, torch::Tensor rstd);
+torch::Tensor norm_act_bwd(torch::Tensor dy, torch::Tensor x,
+                           torch::Tensor mean, torch::Tensor rstd,
+                           torch::Tensor weight, torch::Tensor bias,
+                           double p, int64_t seed, bool training,
+                           torch::Tensor dx);
+int64_t norm_act_bwd_max_blocks();
+int64_t norm_act_waves_per_block();
+int64_t norm_act_max_feats();
+
 void fused_dual_gemm_bf16(torch::Tensor a1, torch::Tensor a2,
                           torch::Tensor w1t, torch::Tensor w2t,
                           torch::Tensor bias, torch::Tensor out) {
@@ -681,4 +662,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "CSR SpMM with fused degree normalization (CDNA4)");
     m.def("fused_dual_gemm_bf16", &fused_dual_gemm_bf16,
           "out = A1@W1 + A2@W2 + bias, one-pass MFMA (CDNA4)");
+    m.def("norm_act_fwd", &norm_act_fwd,
+          "fused LayerNorm+ReLU+dropout forward (CDNA4)");
+    m.def("norm_act_bwd", &norm_act_bwd,
+          "fused LayerNorm+ReLU+dropout backward; returns [2,F] "
+          "(dweight, dbias) (CDNA4)");
+    m.attr("NORM_ACT_BWD_MAX_BLOCKS") = norm_act_bwd_max_blocks();
+    m.attr("NORM_ACT_WAVES_PER_BLOCK") = norm_act_waves_per_block();
+    m.attr("NORM_ACT_MAX_FEATS") = norm_act_max_feats();
 }

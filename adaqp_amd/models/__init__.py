@@ -1,4 +1,6 @@
 from .gcn import DistGCN, DistGCNConv
 from .sage import DistSAGE, DistSAGEConv
+from .norm import FusedNormReluDropout
 
-__all__ = ['DistGCN', 'DistGCNConv', 'DistSAGE', 'DistSAGEConv']
+__all__ = ['DistGCN', 'DistGCNConv', 'DistSAGE', 'DistSAGEConv',
+           'FusedNormReluDropout']

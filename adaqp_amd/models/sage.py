@@ -5,11 +5,14 @@ Reference parity: ``AdaQP/model/distSAGE.py:46-60`` — mean:
 h_neigh includes the self term (handled inside the aggregation op)."""
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from ..ops.dist_agg import dist_aggregate
+from .norm import FusedNormReluDropout, resolve_fused_norm
 from .common import FastLinear, fused_dual_linear, fused_dual_linear_ok
 
 
@@ -45,24 +48,38 @@ class DistSAGEConv(nn.Module):
 class DistSAGE(nn.Module):
     def __init__(self, in_dim: int, hidden_dim: int, out_dim: int,
                  num_layers: int = 3, dropout: float = 0.5,
-                 use_norm: bool = True, aggregator_type: str = 'mean'):
+                 use_norm: bool = True, aggregator_type: str = 'mean',
+                 fused_norm: Optional[bool] = None):
         super().__init__()
         dims = [in_dim] + [hidden_dim] * (num_layers - 1) + [out_dim]
         self.convs = nn.ModuleList(
             [DistSAGEConv(dims[i], dims[i + 1], layer=i,
                           aggregator_type=aggregator_type)
              for i in range(num_layers)])
-        self.norms = nn.ModuleList(
-            [nn.LayerNorm(hidden_dim, elementwise_affine=True)
-             for _ in range(num_layers - 1)]) if use_norm else None
+        # fused_norm: norms[i] does LayerNorm -> ReLU -> the next layer's
+        # dropout in one op (None = on iff ADAQP_FUSED_NORM=1). Same function
+        # as the unfused stack up to the dropout RNG stream. Without
+        # use_norm there is nothing to fuse and the flag has no effect.
+        self.fused_norm = use_norm and resolve_fused_norm(fused_norm)
+        if self.fused_norm:
+            self.norms = nn.ModuleList(
+                [FusedNormReluDropout(hidden_dim, dropout, layer=i)
+                 for i in range(num_layers - 1)])
+        else:
+            self.norms = nn.ModuleList(
+                [nn.LayerNorm(hidden_dim, elementwise_affine=True)
+                 for _ in range(num_layers - 1)]) if use_norm else None
         self.dropout = nn.Dropout(dropout)
 
     def forward(self, engine, feats: Tensor) -> Tensor:
         h = feats
         for i, conv in enumerate(self.convs):
-            h = self.dropout(h) if i > 0 else h
+            h = self.dropout(h) if i > 0 and not self.fused_norm else h
             h = conv(engine, h)
             if i < len(self.convs) - 1:
+                if self.fused_norm:
+                    h = self.norms[i](h)
+                    continue
                 if self.norms is not None:
                     h = self.norms[i](h)
                 h = torch.relu(h)

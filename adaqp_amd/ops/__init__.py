@@ -1,6 +1,8 @@
 from .dist_agg import DistAgg, dist_aggregate, fp_exchange, qt_exchange
 from .kernels import spmm, SpmmView, mixed_quantize, mixed_dequantize, native, has_native
+from .norm_act import norm_relu_dropout, norm_relu_dropout_torch
 
 __all__ = ['DistAgg', 'dist_aggregate', 'fp_exchange', 'qt_exchange',
            'spmm', 'SpmmView', 'mixed_quantize', 'mixed_dequantize',
-           'native', 'has_native']
+           'native', 'has_native', 'norm_relu_dropout',
+           'norm_relu_dropout_torch']

@@ -55,6 +55,8 @@ class Trainer:
             v = getattr(args, k, None)
             if v is not None:
                 rt[k] = v
+        if getattr(args, 'fused_norm', False):     # CLI overrides the config
+            self.cfg['model']['fused_norm'] = True
         self.mode = RunMode(args.mode)
         self.model_type = MODEL_MAP[args.model_name]
         self.comm = Communicator(backend=getattr(args, 'backend', None),
@@ -156,7 +158,8 @@ class Trainer:
         m = self.cfg['model']
         cls = DistGCN if self.model_type == DistGNNType.DistGCN else DistSAGE
         kwargs = dict(num_layers=m['num_layers'], dropout=m['dropout'],
-                      use_norm=m['use_norm'])
+                      use_norm=m['use_norm'],
+                      fused_norm=m.get('fused_norm'))
         if cls is DistSAGE:
             kwargs['aggregator_type'] = m['aggregator_type']
         self.model = cls(self.feat_dim, m['hidden_dim'], self.num_classes,

@@ -15,7 +15,7 @@ import argparse
 from adaqp_amd.runtime.trainer import Trainer
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument('--dataset', type=str, default='reddit',
                    choices=['reddit', 'yelp', 'ogbn-products', 'amazonProducts'])
@@ -50,7 +50,15 @@ def main():
     p.add_argument('--time_breakdown', action='store_true',
                    help='enable per-epoch comm/quant/agg span timing '
                         '(adds sync fences; use rocprofv3 for kernel evidence)')
-    args = p.parse_args()
+    p.add_argument('--fused_norm', action='store_true',
+                   help='fused LayerNorm+ReLU+dropout between layers '
+                        '(overrides the config; ADAQP_FUSED_NORM=1 is the '
+                        'env switch when neither sets it)')
+    return p
+
+
+def main():
+    args = build_parser().parse_args()
 
     # allow plain `python main.py` without torchrun (world_size 1)
     import os

@@ -20,7 +20,8 @@ setup(
     ext_modules=[
         CUDAExtension(
             name='adaqp_amd._C',
-            sources=['adaqp_amd/csrc/kernels.hip'],
+            sources=['adaqp_amd/csrc/kernels.hip',
+                     'adaqp_amd/csrc/norm_act.hip'],
             extra_compile_args={'cxx': ['-O3'],
                                 'nvcc': ['-O3', '--offload-arch=gfx950']},
         )
