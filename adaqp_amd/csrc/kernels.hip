@@ -207,24 +207,43 @@ __global__ void quant_unpack_kernel(
 // each XCD a contiguous chunk of work items so clustered neighbor rows
 // hit the same L2 (guide §5.5 T1).
 // ---------------------------------------------------------------------------
+// Value stored to y for the fp32 SpMM result o. With an epilogue addend
+// (ad != nullptr) o is first rounded to T — the value spmm alone stores —
+// and the addend is added with a rounding of its own, never contracted
+// into the dst-scale multiply that produced o, so y equals torch's
+// ``spmm(...) + addend`` bit for bit (bf16: round, widen, add, round).
+template <typename T>
+__device__ __forceinline__ T round_add(float o, const T* ad) {
+#pragma clang fp contract(off)
+    if constexpr (sizeof(T) == 2) {
+        uint16_t h = f32_to_bf16(o);
+        if (ad) h = f32_to_bf16(bf16_to_f32(h) + bf16_to_f32(*ad));
+        return h;
+    } else {
+        return ad ? o + *ad : o;
+    }
+}
+
 // One wavefront per split row: y[rows[j]] = sum of its partial slots
-// [part_ptr[j], part_ptr[j+1]) in slot order (an empty range writes zeros).
+// [part_ptr[j], part_ptr[j+1]) in slot order (an empty range writes zeros),
+// plus the row's addend when one is given.
 template <typename T>
 __global__ void combine_parts_kernel(T* __restrict__ y,
                                      const float* __restrict__ part,
                                      const int32_t* __restrict__ rows,
                                      const int32_t* __restrict__ part_ptr,
+                                     const T* __restrict__ addend,
                                      int64_t n, int64_t F) {
     const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
                       + threadIdx.x / WAVE;
     if (wid >= n) return;
     T* p = y + (int64_t)rows[wid] * F;
+    const T* a = addend ? addend + (int64_t)rows[wid] * F : nullptr;
     const int64_t p0 = part_ptr[wid], p1 = part_ptr[wid + 1];
     for (int64_t f = threadIdx.x & (WAVE - 1); f < F; f += WAVE) {
         float acc = 0.f;
         for (int64_t q = p0; q < p1; ++q) acc += part[q * F + f];
-        if constexpr (sizeof(T) == 2) p[f] = f32_to_bf16(acc);
-        else p[f] = acc;
+        p[f] = round_add<T>(acc, a ? a + f : nullptr);
     }
 }
 
@@ -245,9 +264,8 @@ __global__ void spmm_csr_kernel(
     const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
     const int32_t* __restrict__ seg_row, const int32_t* __restrict__ seg_e0,
     const int32_t* __restrict__ seg_e1, const int32_t* __restrict__ seg_part,
-    float* __restrict__ part,
+    float* __restrict__ part, const T* __restrict__ addend,
     int64_t n_seg, int64_t F, int64_t n_local) {
-    constexpr bool BF = sizeof(T) == 2;
     constexpr int NB = VE * sizeof(T);
     using Raw = typename RawVec<NB>::type;
     const int rows_per_block = blockDim.x / SW;
@@ -329,18 +347,162 @@ __global__ void spmm_csr_kernel(
             }
             T* yr = y + r * F + f0;
             if (slot < 0) {
+                Raw av = {};
+                if (addend)
+                    av = *reinterpret_cast<const Raw*>(addend + r * F + f0);
+                const T* ad = reinterpret_cast<const T*>(&av);
                 T outv[VE];
 #pragma unroll
-                for (int k = 0; k < VE; ++k) {
-                    const float o = (acc0[k] + acc1[k]) * ds;
-                    if constexpr (BF) outv[k] = f32_to_bf16(o);
-                    else outv[k] = o;
-                }
+                for (int k = 0; k < VE; ++k)
+                    outv[k] = round_add<T>((acc0[k] + acc1[k]) * ds,
+                                           addend ? ad + k : nullptr);
                 *reinterpret_cast<Raw*>(yr) = *reinterpret_cast<const Raw*>(outv);
             } else {
                 // long row split across segments: fp32 partial into this
                 // segment's own slot, summed by combine_parts_kernel
                 float* pp = part + slot * F + f0;
+#pragma unroll
+                for (int k = 0; k < VE; ++k)
+                    pp[k] = (acc0[k] + acc1[k]) * ds;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// spmm_csr, wave-uniform index path (the SW == 64 case: one whole wavefront
+// per segment). Same result as spmm_csr_kernel<64, T, VE> bit for bit — edge
+// j of a segment goes into accumulator j & 1 in increasing j, one fmaf each,
+// epilogue (acc0 + acc1) * ds — but the per-edge integer work is done once
+// per wave instead of once per lane: the segment record is read through
+// scalar registers, each chunk of 64 column indices (and their src_scale
+// values) is fetched with ONE coalesced load, lane l holding edge eb + l,
+// and every edge's column/scale is broadcast with readlane, so the
+// local/remote select and the row base address are scalar arithmetic. Only
+// the 16-byte row loads and the FMAs remain per lane.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float readlane_f32(float v, int l) {
+    return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), l));
+}
+
+// accumulate edges [0, n) of one index chunk held one-per-lane in myc/mys:
+// batches of 4, then 2, then 1 row loads in flight, as spmm_csr_kernel.
+// Every batch starts at an even j (chunks before a segment's last hold 64
+// edges), so edge j + u goes to accumulator u & 1. (Eight loads in flight
+// measured the same as four on the products-like microbench: the gather
+// runs at the memory system's rate either way.)
+template <typename T, int VE, bool SS>
+__device__ __forceinline__ void spmm_chunk(
+    int myc, float mys, int n, const T* __restrict__ xl,
+    const T* __restrict__ xr, int64_t F, int64_t n_local, int64_t f0,
+    float (&acc0)[VE], float (&acc1)[VE]) {
+    using Raw = typename RawVec<VE * sizeof(T)>::type;
+    // columns, n_local and F all fit 32 bits (host-checked): the select
+    // and the 32x32->64 row offset stay short scalar sequences
+    const uint32_t nl = (uint32_t)n_local, Fu = (uint32_t)F;
+    auto row = [&](int j) -> const T* {
+        const uint32_t c = (uint32_t)__builtin_amdgcn_readlane(myc, j);
+        const bool loc = c < nl;
+        const T* base = loc ? xl : xr;
+        return base + (uint64_t)(loc ? c : c - nl) * Fu + f0;
+    };
+    auto batch = [&](int j, auto nb_tag) {
+        constexpr int NB = decltype(nb_tag)::value;
+        float s[NB];
+        Raw r[NB];
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            s[u] = SS ? readlane_f32(mys, j + u) : 1.f;
+            r[u] = *reinterpret_cast<const Raw*>(row(j + u));
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            const T* v = reinterpret_cast<const T*>(&r[u]);
+#pragma unroll
+            for (int k = 0; k < VE; ++k) {
+                if (u & 1) acc1[k] = fmaf(to_f32<T>(v[k]), s[u], acc1[k]);
+                else acc0[k] = fmaf(to_f32<T>(v[k]), s[u], acc0[k]);
+            }
+        }
+    };
+    int j = 0;
+    for (; j + 3 < n; j += 4) batch(j, std::integral_constant<int, 4>{});
+    for (; j + 1 < n; j += 2) batch(j, std::integral_constant<int, 2>{});
+    if (j < n) batch(j, std::integral_constant<int, 1>{});
+}
+
+template <typename T, int VE>
+__global__ void spmm_csr_wave_kernel(
+    const int32_t* __restrict__ indices,
+    const T* __restrict__ xl, const T* __restrict__ xr,
+    T* __restrict__ y,
+    const float* __restrict__ src_scale, const float* __restrict__ dst_scale,
+    const int32_t* __restrict__ seg_row, const int32_t* __restrict__ seg_e0,
+    const int32_t* __restrict__ seg_e1, const int32_t* __restrict__ seg_part,
+    float* __restrict__ part, const T* __restrict__ addend,
+    int64_t n_seg, int64_t F, int64_t n_local) {
+    using Raw = typename RawVec<VE * sizeof(T)>::type;
+    const int waves_per_block = blockDim.x / WAVE;
+    // same bijective XCD swizzle as spmm_csr_kernel
+    const int64_t nwg = gridDim.x;
+    const int64_t q = nwg / 8, rem = nwg % 8;
+    const int64_t xcd = blockIdx.x % 8, idx = blockIdx.x / 8;
+    const int64_t swz = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + idx;
+    // the wave id is uniform but not provably so: readfirstlane it, and
+    // everything read through it lands in scalar registers
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t stride = nwg * waves_per_block;
+
+    for (int64_t it = swz * waves_per_block + wave; it < n_seg; it += stride) {
+        const int64_t r = __builtin_amdgcn_readfirstlane(seg_row[it]);
+        const int e0 = __builtin_amdgcn_readfirstlane(seg_e0[it]);
+        const int e1 = __builtin_amdgcn_readfirstlane(seg_e1[it]);
+        const int slot = __builtin_amdgcn_readfirstlane(seg_part[it]);
+        const float ds = dst_scale
+            ? __uint_as_float(__builtin_amdgcn_readfirstlane(
+                  __float_as_uint(dst_scale[r])))
+            : 1.f;
+        for (int64_t fc = 0; fc < F; fc += (int64_t)WAVE * VE) {
+            // lanes past F (F < 64*VE, or the last chunk of a wider row)
+            // still take part in the index loads; they gather from
+            // feature 0 (in bounds, VE | F) and store nothing
+            const int64_t fl = fc + (int64_t)lane * VE;
+            const bool active = fl < F;
+            const int64_t f0 = active ? fl : 0;
+            float acc0[VE], acc1[VE];
+#pragma unroll
+            for (int k = 0; k < VE; ++k) { acc0[k] = 0.f; acc1[k] = 0.f; }
+            for (int eb = e0; eb < e1; eb += WAVE) {
+                const int n = min(e1 - eb, WAVE);
+                int myc = 0;
+                float mys = 1.f;
+                if (lane < n) {
+                    myc = indices[eb + lane];
+                    if (src_scale) mys = src_scale[myc];
+                }
+                if (src_scale)
+                    spmm_chunk<T, VE, true>(myc, mys, n, xl, xr, F, n_local,
+                                            f0, acc0, acc1);
+                else
+                    spmm_chunk<T, VE, false>(myc, mys, n, xl, xr, F, n_local,
+                                             f0, acc0, acc1);
+            }
+            if (!active) continue;
+            if (slot < 0) {
+                Raw av = {};
+                if (addend)
+                    av = *reinterpret_cast<const Raw*>(addend + r * F + f0);
+                const T* ad = reinterpret_cast<const T*>(&av);
+                T outv[VE];
+#pragma unroll
+                for (int k = 0; k < VE; ++k)
+                    outv[k] = round_add<T>((acc0[k] + acc1[k]) * ds,
+                                           addend ? ad + k : nullptr);
+                *reinterpret_cast<Raw*>(y + r * F + f0) =
+                    *reinterpret_cast<const Raw*>(outv);
+            } else {
+                float* pp = part + (int64_t)slot * F + f0;
 #pragma unroll
                 for (int k = 0; k < VE; ++k)
                     pp[k] = (acc0[k] + acc1[k]) * ds;
@@ -512,7 +674,8 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
               torch::Tensor dst_scale, torch::Tensor seg_row,
               torch::Tensor seg_e0, torch::Tensor seg_e1,
               torch::Tensor seg_part, torch::Tensor zero_rows,
-              torch::Tensor part_ptr, int64_t n_part) {
+              torch::Tensor part_ptr, int64_t n_part,
+              torch::Tensor addend, bool wave_index) {
     CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
     const bool bf16 = xl.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(bf16 || xl.scalar_type() == torch::kFloat32,
@@ -527,6 +690,16 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
         TORCH_CHECK(xr.size(1) == F, "remote feature dim mismatch");
         TORCH_CHECK(xr.scalar_type() == xl.scalar_type(), "x dtype mismatch");
         xr_ptr = xr.data_ptr();
+    }
+    // optional epilogue addend: y = spmm + addend ([nrows, F], y's dtype)
+    const void* ad_ptr = nullptr;
+    if (addend.dim() == 2) {        // a 1-D empty tensor means "none"
+        CHECK_DEV(addend); CHECK_CONTIG(addend);
+        TORCH_CHECK(addend.size(0) == y.size(0) && addend.size(1) == F,
+                    "addend must be [nrows, F]");
+        TORCH_CHECK(addend.scalar_type() == y.scalar_type(),
+                    "addend/y dtype mismatch");
+        ad_ptr = addend.numel() ? addend.data_ptr() : nullptr;
     }
     auto s = cur_stream();
     TORCH_CHECK(seg_part.scalar_type() == torch::kInt32 &&
@@ -547,12 +720,13 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
             combine_parts_kernel<ushort><<<zg, zb, 0, s>>>(
                 reinterpret_cast<ushort*>(y.data_ptr()),
                 part.data_ptr<float>(), zero_rows.data_ptr<int32_t>(),
-                part_ptr.data_ptr<int32_t>(), zero_rows.numel(), F);
+                part_ptr.data_ptr<int32_t>(),
+                reinterpret_cast<const ushort*>(ad_ptr), zero_rows.numel(), F);
         else
             combine_parts_kernel<float><<<zg, zb, 0, s>>>(
                 y.data_ptr<float>(), part.data_ptr<float>(),
                 zero_rows.data_ptr<int32_t>(), part_ptr.data_ptr<int32_t>(),
-                zero_rows.numel(), F);
+                reinterpret_cast<const float*>(ad_ptr), zero_rows.numel(), F);
     };
     if (n_seg == 0) { combine(); return; }
     // largest vector width dividing F (keeps every row-base load aligned)
@@ -560,6 +734,8 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
     while (ve > 1 && F % ve) ve >>= 1;
     if (bf16 && ve == 1) ve = 2;              // bf16 loads are >= one dword
     TORCH_CHECK(!bf16 || F % 2 == 0, "bf16 spmm needs even feature dim");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(ad_ptr) % (ve * (bf16 ? 2 : 4)) == 0,
+                "addend rows must be aligned to the vector load width");
     // sub-wavefront width: smallest of {16,32,64} covering F with ve/lane
     int sw = 16;
     while (sw < 64 && (int64_t)sw * ve < F) sw *= 2;
@@ -584,11 +760,28 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
         constexpr int SWC = decltype(sw_tag)::value;
         using TC = typename decltype(t_tag)::type;
         constexpr int VEC = decltype(ve_tag)::value;
+        // SW == 64: the whole wavefront owns one segment, so the index
+        // work can be wave-uniform; wave_index selects that kernel, the
+        // per-lane one stays the default (A/B runs, the equality test)
+        if constexpr (SWC == 64) {
+            if (wave_index) {
+                TORCH_CHECK(F < (1ll << 31) && n_local < (1ll << 31),
+                            "spmm_csr: F and n_local must fit 31 bits");
+                spmm_csr_wave_kernel<TC, VEC><<<grid, block, 0, s>>>(
+                    ind_p, reinterpret_cast<const TC*>(xl.data_ptr()),
+                    reinterpret_cast<const TC*>(xr_ptr),
+                    reinterpret_cast<TC*>(y.data_ptr()), ss_p, ds_p,
+                    sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(),
+                    reinterpret_cast<const TC*>(ad_ptr), n_seg, F, n_local);
+                return;
+            }
+        }
         spmm_csr_kernel<SWC, TC, VEC><<<grid, block, 0, s>>>(
             ind_p, reinterpret_cast<const TC*>(xl.data_ptr()),
             reinterpret_cast<const TC*>(xr_ptr),
             reinterpret_cast<TC*>(y.data_ptr()), ss_p, ds_p,
-            sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(), n_seg, F, n_local);
+            sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(),
+            reinterpret_cast<const TC*>(ad_ptr), n_seg, F, n_local);
     };
     struct FT { using type = float; };
     struct BT { using type = ushort; };
@@ -629,6 +822,9 @@ int64_t norm_act_bwd_max_blocks();
 int64_t norm_act_waves_per_block();
 int64_t norm_act_max_feats();
 
+// colsum.hip
+torch::Tensor colsum(torch::Tensor g);
+
 void fused_dual_gemm_bf16(torch::Tensor a1, torch::Tensor a2,
                           torch::Tensor w1t, torch::Tensor w2t,
                           torch::Tensor bias, torch::Tensor out) {
@@ -659,7 +855,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("quant_unpack", &quant_unpack,
           "fused dequantize+scatter (CDNA4)");
     m.def("spmm_csr", &spmm_csr,
-          "CSR SpMM with fused degree normalization (CDNA4)");
+          "CSR SpMM with fused degree normalization and an optional "
+          "epilogue addend (CDNA4)",
+          pybind11::arg("indices"), pybind11::arg("xl"), pybind11::arg("xr"),
+          pybind11::arg("y"), pybind11::arg("src_scale"),
+          pybind11::arg("dst_scale"), pybind11::arg("seg_row"),
+          pybind11::arg("seg_e0"), pybind11::arg("seg_e1"),
+          pybind11::arg("seg_part"), pybind11::arg("zero_rows"),
+          pybind11::arg("part_ptr"), pybind11::arg("n_part"),
+          pybind11::arg("addend"), pybind11::arg("wave_index") = false);
+    m.def("colsum", &colsum,
+          "deterministic column sum of a [N,F] fp32/bf16 matrix, fp32 "
+          "accumulate (CDNA4)");
     m.def("fused_dual_gemm_bf16", &fused_dual_gemm_bf16,
           "out = A1@W1 + A2@W2 + bias, one-pass MFMA (CDNA4)");
     m.def("norm_act_fwd", &norm_act_fwd,

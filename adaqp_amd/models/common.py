@@ -5,12 +5,22 @@ ROCm lowers to a strided column reduction running at ~0.2 TB/s for the
 [N, 256] grads this model produces (measured: 3.8 ms for 0.73M x 256 —
 ~10% of an epoch). Computing it as ``ones[1,N] @ grad`` instead routes
 it through rocBLAS at memory bandwidth.
+
+``ADAQP_COLSUM=1`` switches the GPU bias gradient to the native one-pass
+``colsum`` kernel (csrc/colsum.hip; 0.40 vs 1.52 ms on N x 256 fp32). It
+sums in another order than the GEMM, so fp32 bias grads differ in the
+last bits and a training run drifts away from the default path's bit
+for bit; that is why it is opt-in.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
 from torch import Tensor
+
+from ..ops.kernels import colsum
 
 _ones_cache: dict = {}
 
@@ -24,6 +34,17 @@ def _ones_row(n: int, device, dtype) -> Tensor:
             _ones_cache.clear()
         _ones_cache[key] = t
     return t[:, :n]
+
+
+def bias_grad(g: Tensor) -> Tensor:
+    """Column sum of the contiguous upstream grad ``g`` [N, F], in g's
+    dtype: ``ones[1,N] @ g`` on the GPU (``colsum`` with ADAQP_COLSUM=1),
+    ``g.sum(0)`` on the CPU."""
+    if not g.is_cuda:
+        return g.sum(dim=0)
+    if os.environ.get('ADAQP_COLSUM') == '1':
+        return colsum(g)
+    return (_ones_row(g.shape[0], g.device, g.dtype) @ g).reshape(-1)
 
 
 class _LinearBiasFn(torch.autograd.Function):
@@ -40,10 +61,7 @@ class _LinearBiasFn(torch.autograd.Function):
         gw = x.t() @ g if ctx.needs_input_grad[1] else None
         gb = None
         if ctx.needs_input_grad[2]:
-            if g.is_cuda:
-                gb = (_ones_row(g.shape[0], g.device, g.dtype) @ g).reshape(-1)
-            else:
-                gb = g.sum(dim=0)
+            gb = bias_grad(g)
         return gx, gw, gb
 
 
@@ -103,7 +121,7 @@ class _FusedDualLinearFn(torch.autograd.Function):
         gw2 = h.t() @ g if ctx.needs_input_grad[3] else None
         gb = None
         if ctx.needs_input_grad[4]:
-            gb = (_ones_row(g.shape[0], g.device, g.dtype) @ g).reshape(-1)
+            gb = bias_grad(g)
         return gx, gh, gw1, gw2, gb, gb
 
 
@@ -134,3 +152,70 @@ def fused_dual_linear(x, h, lin1: 'FastLinear', lin2: 'FastLinear') -> Tensor:
         x.to(dt), h.to(dt), lin1.weight.to(dt), lin2.weight.to(dt),
         lin1.bias.to(dt) if lin1.bias is not None else None,
         lin2.bias.to(dt) if lin2.bias is not None else None)
+
+
+class _SageMeanFn(torch.autograd.Function):
+    """The SAGE 'mean' layer, ``fc_self(x[:I]) + fc_neigh(mean_agg(x))``, as
+    ONE autograd node. Forward is the unfused formulation call for call
+    (propagate, two addmm, one add). What the single node buys is the
+    backward: the input grad ``g @ W_self^T + A^T D^-1 (g @ W_neigh^T)`` is
+    written by the backward SpMM's epilogue (``addend``) instead of by a
+    zero-fill + slice copy + accumulate pass over [N, F], and the two
+    biases, which receive the same upstream grad, share one column sum.
+
+    ``w1/w2/b1/b2`` arrive already cast (bf16 under autocast), as in
+    FastLinear.forward, so fp32 master weights get fp32 grads through the
+    cast backward. ``x`` is cast inside, as DistAgg does: when its dtype
+    differs from the compute dtype (fp32 activations under bf16 autocast)
+    the two input-grad terms are added in x's dtype, exactly as autograd
+    accumulated them, and the SpMM addend is not used."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, w1: Tensor, w2: Tensor, b1: Tensor,
+                b2: Tensor, engine, layer: int, is_train: bool) -> Tensor:
+        from ..ops.dist_agg import propagate
+        from ..helpers import PropagationMode
+        num_inner = engine.graph.num_inner
+        xa = x.to(engine.compute_dtype).contiguous()
+        h = propagate(engine, xa, layer, is_train, PropagationMode.Forward)
+        xs = x[:num_inner].to(w1.dtype)
+        ctx.engine, ctx.layer, ctx.in_dtype = engine, layer, x.dtype
+        ctx.in_rows = x.shape[0]
+        ctx.save_for_backward(xs, h, w1, w2)
+        return torch.addmm(b1, xs, w1) + torch.addmm(b2, h, w2)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        from ..ops.dist_agg import propagate
+        from ..helpers import PropagationMode
+        xs, h, w1, w2 = ctx.saved_tensors
+        engine = ctx.engine
+        g = g.contiguous()
+        gx = None
+        if ctx.needs_input_grad[0]:
+            assert ctx.in_rows == engine.graph.num_inner
+            gh = (g @ w2.t()).to(engine.compute_dtype).contiguous()
+            gx_self = g @ w1.t()
+            if gx_self.dtype == gh.dtype == ctx.in_dtype:
+                gx = propagate(engine, gh, ctx.layer, True,
+                               PropagationMode.Backward, addend=gx_self)
+            else:
+                gx = propagate(engine, gh, ctx.layer, True,
+                               PropagationMode.Backward).to(ctx.in_dtype)
+                gx.add_(gx_self)        # promotes gx_self: exact widening
+        gw1 = xs.t() @ g if ctx.needs_input_grad[1] else None
+        gw2 = h.t() @ g if ctx.needs_input_grad[2] else None
+        gb = bias_grad(g) if (ctx.needs_input_grad[3]
+                           or ctx.needs_input_grad[4]) else None
+        return gx, gw1, gw2, gb, gb, None, None, None
+
+
+def sage_mean_layer(engine, x: Tensor, lin1: 'FastLinear', lin2: 'FastLinear',
+                    layer: int, is_train: bool) -> Tensor:
+    """lin1(x[:num_inner]) + lin2(mean aggregation of x) through
+    :class:`_SageMeanFn`; weight/bias casts mirror FastLinear.forward."""
+    w1, w2, b1, b2 = lin1.weight, lin2.weight, lin1.bias, lin2.bias
+    if torch.is_autocast_enabled('cuda') and x.is_cuda:
+        dt = torch.get_autocast_dtype('cuda')
+        w1, w2, b1, b2 = w1.to(dt), w2.to(dt), b1.to(dt), b2.to(dt)
+    return _SageMeanFn.apply(x, w1, w2, b1, b2, engine, layer, is_train)

@@ -13,7 +13,10 @@ from torch import Tensor
 
 from ..ops.dist_agg import dist_aggregate
 from .norm import FusedNormReluDropout, resolve_fused_norm
-from .common import FastLinear, fused_dual_linear, fused_dual_linear_ok
+import os
+
+from .common import (FastLinear, fused_dual_linear, fused_dual_linear_ok,
+                     sage_mean_layer)
 
 
 class DistSAGEConv(nn.Module):
@@ -33,6 +36,19 @@ class DistSAGEConv(nn.Module):
             self.fc_self.reset_parameters()
 
     def forward(self, engine, x: Tensor) -> Tensor:
+        # gradients being recorded: the 'mean' layer is one autograd node
+        # (same forward calls; fused input-grad add and a shared bias
+        # grad in backward). The opt-in ADAQP_FUSED_SAGE path and the
+        # eval / no-grad path stay on the formulation below. The node's
+        # backward writes the [num_inner, F] aggregation grad as the grad
+        # of x, so x must hold exactly the inner rows (it always does when
+        # it comes from the layer stack).
+        if (self.aggregator_type == 'mean' and torch.is_grad_enabled()
+                and self.fc_self.bias is not None
+                and x.shape[0] == engine.graph.num_inner
+                and os.environ.get('ADAQP_FUSED_SAGE') != '1'):
+            return sage_mean_layer(engine, x, self.fc_self, self.fc_neigh,
+                                   self.layer, self.training)
         h_neigh = dist_aggregate(x, engine, self.layer, self.training)
         if self.aggregator_type == 'mean':
             x_self = x[:engine.graph.num_inner]

@@ -112,6 +112,13 @@ import os as _os
 # slower); cross-box deltas on other datasets are within run-to-run
 # noise (profiles/r02_NOTES.md). ADAQP_SEG_EDGES overrides.
 SEG_EDGES = int(_os.environ.get('ADAQP_SEG_EDGES', '256'))
+# SW == 64 SpMM (one wavefront per segment: fp32 F > 128, bf16 F > 256):
+# False = the per-lane index kernel, True = the wave-uniform index kernel.
+# Both give the same bits; the wave-uniform one measured no faster (the
+# gather runs at the memory system's rate: profiles/spmm_scalar_NOTES.md),
+# so it stays behind this switch. ADAQP_SPMM_WAVE_INDEX=1 turns it on
+# (read once, here).
+WAVE_INDEX = _os.environ.get('ADAQP_SPMM_WAVE_INDEX', '0') == '1'
 
 
 def _auto_seg(num_edges: int, num_rows: int) -> int:
@@ -224,7 +231,8 @@ class SpmmView:
 
 def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
          src_scale: Optional[Tensor], dst_scale: Optional[Tensor],
-         out: Optional[Tensor] = None) -> Tensor:
+         out: Optional[Tensor] = None, addend: Optional[Tensor] = None,
+         wave_index: Optional[bool] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
     Columns < len(x_local) read x_local; the rest read x_remote (the
@@ -233,6 +241,10 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
     ``out`` (GPU path): write into this [nrows, F] contiguous tensor —
     lets the decomposed path target row slices of ONE output so the
     central/marginal results need no torch.cat afterwards.
+    ``addend``: optional [nrows, F] contiguous tensor of y's dtype; the
+    result is ``spmm(...) + addend`` bit for bit, added in the kernel's
+    epilogue instead of a separate pass.
+    ``wave_index``: which SW == 64 kernel runs (None = WAVE_INDEX).
     """
     indptr, indices, num_rows = view.indptr, view.indices, view.nrows
     if not x_local.is_cuda and view.col_blocked:
@@ -246,13 +258,19 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
         else:
             assert out.is_contiguous() and out.shape[0] == num_rows
         empty = torch.empty(0, device=x_local.device)
+        if addend is not None:
+            assert (addend.is_contiguous() and addend.dtype == out.dtype
+                    and addend.shape == out.shape)
         native().spmm_csr(indices, x_local,
                           x_remote if x_remote is not None else empty, out,
                           src_scale if src_scale is not None else empty,
                           dst_scale if dst_scale is not None else empty,
                           view.seg_row, view.seg_e0, view.seg_e1,
                           view.seg_part, view.zero_rows, view.part_ptr,
-                          view.n_part)
+                          view.n_part,
+                          addend if addend is not None else empty,
+                          bool(WAVE_INDEX if wave_index is None
+                               else wave_index))
         return out
     x = (torch.cat([x_local, x_remote], dim=0)
          if x_remote is not None and x_remote.numel() else x_local)
@@ -270,7 +288,21 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
     y = torch.sparse.mm(sp, xs.float()).to(x.dtype)
     if dst_scale is not None:
         y = y * dst_scale[:, None]
+    if addend is not None:
+        y = y + addend
     if out is not None:
         out.copy_(y)
         return out
     return y
+
+
+# --------------------------------------------------------------------------
+# column sum (bias gradient)
+# --------------------------------------------------------------------------
+
+def colsum(g: Tensor) -> Tensor:
+    """``g.sum(0)`` of a [N, F] matrix in g's dtype. GPU: one deterministic
+    pass of the native kernel (fp32 accumulate, fixed order)."""
+    if g.is_cuda:
+        return native().colsum(g.contiguous())
+    return g.sum(dim=0)

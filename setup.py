@@ -21,7 +21,8 @@ setup(
         CUDAExtension(
             name='adaqp_amd._C',
             sources=['adaqp_amd/csrc/kernels.hip',
-                     'adaqp_amd/csrc/norm_act.hip'],
+                     'adaqp_amd/csrc/norm_act.hip',
+                     'adaqp_amd/csrc/colsum.hip'],
             extra_compile_args={'cxx': ['-O3'],
                                 'nvcc': ['-O3', '--offload-arch=gfx950']},
         )
