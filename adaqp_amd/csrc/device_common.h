@@ -42,3 +42,31 @@ template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; 
 template <> __device__ __forceinline__ float to_f32<ushort>(ushort v) {
     return bf16_to_f32(v);
 }
+
+// ---------------------------------------------------------------------------
+// SpMM helpers shared by kernels.hip and spmm_packed.hip
+// ---------------------------------------------------------------------------
+// Value stored to y for the fp32 SpMM result o. With an epilogue addend
+// (ad != nullptr) o is first rounded to T — the value spmm alone stores —
+// and the addend is added with a rounding of its own, never contracted
+// into the dst-scale multiply that produced o, so y equals torch's
+// ``spmm(...) + addend`` bit for bit (bf16: round, widen, add, round).
+template <typename T>
+__device__ __forceinline__ T round_add(float o, const T* ad) {
+#pragma clang fp contract(off)
+    if constexpr (sizeof(T) == 2) {
+        uint16_t h = f32_to_bf16(o);
+        if (ad) h = f32_to_bf16(bf16_to_f32(h) + bf16_to_f32(*ad));
+        return h;
+    } else {
+        return ad ? o + *ad : o;
+    }
+}
+
+
+// raw load/store type of NB bytes
+template <int NB> struct RawVec;
+template <> struct RawVec<16> { using type = uint4; };
+template <> struct RawVec<8>  { using type = uint2; };
+template <> struct RawVec<4>  { using type = unsigned; };
+template <> struct RawVec<2>  { using type = ushort; };

@@ -207,23 +207,8 @@ __global__ void quant_unpack_kernel(
 // each XCD a contiguous chunk of work items so clustered neighbor rows
 // hit the same L2 (guide §5.5 T1).
 // ---------------------------------------------------------------------------
-// Value stored to y for the fp32 SpMM result o. With an epilogue addend
-// (ad != nullptr) o is first rounded to T — the value spmm alone stores —
-// and the addend is added with a rounding of its own, never contracted
-// into the dst-scale multiply that produced o, so y equals torch's
-// ``spmm(...) + addend`` bit for bit (bf16: round, widen, add, round).
-template <typename T>
-__device__ __forceinline__ T round_add(float o, const T* ad) {
-#pragma clang fp contract(off)
-    if constexpr (sizeof(T) == 2) {
-        uint16_t h = f32_to_bf16(o);
-        if (ad) h = f32_to_bf16(bf16_to_f32(h) + bf16_to_f32(*ad));
-        return h;
-    } else {
-        return ad ? o + *ad : o;
-    }
-}
-
+// round_add (the value stored to y, with the optional epilogue addend) and
+// RawVec live in device_common.h, shared with spmm_packed.hip
 // One wavefront per split row: y[rows[j]] = sum of its partial slots
 // [part_ptr[j], part_ptr[j+1]) in slot order (an empty range writes zeros),
 // plus the row's addend when one is given.
@@ -250,12 +235,6 @@ __global__ void combine_parts_kernel(T* __restrict__ y,
 // VE = elements per lane per load; chosen host-side as the largest of
 // {8,4,2}(bf16) / {4,2,1}(f32) dividing F, so every row-base load of
 // width VE*sizeof(T) is aligned (rows are x + c*F*sizeof(T)).
-template <int NB> struct RawVec;
-template <> struct RawVec<16> { using type = uint4; };
-template <> struct RawVec<8>  { using type = uint2; };
-template <> struct RawVec<4>  { using type = unsigned; };
-template <> struct RawVec<2>  { using type = ushort; };
-
 template <int SW, typename T, int VE>
 __global__ void spmm_csr_kernel(
     const int32_t* __restrict__ indices,   // int32: halves index bytes
@@ -610,6 +589,20 @@ fused_dual_gemm_bf16_kernel(
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
+// spmm_packed.hip
+bool spmm_packable(int64_t F);
+int64_t packed_meta_bytes(int64_t F);
+int64_t packed_row_stride(int64_t F);
+int64_t packed_buffer_bytes(int64_t n, int64_t F);
+torch::Tensor pack_rows(torch::Tensor x);
+void launch_spmm_packed(
+    dim3 grid, dim3 block, hipStream_t s, int depth,
+    const int32_t* indices, const float* xl, const float* xr,
+    const uint8_t* pk, float* y, const float* src_scale,
+    const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
+    const int32_t* seg_e1, const int32_t* seg_part, float* part,
+    const float* addend, int64_t n_seg, int64_t F, int64_t n_local);
+
 static inline hipStream_t cur_stream() {
     return at::cuda::getCurrentHIPStream().stream();
 }
@@ -675,7 +668,8 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
               torch::Tensor seg_e0, torch::Tensor seg_e1,
               torch::Tensor seg_part, torch::Tensor zero_rows,
               torch::Tensor part_ptr, int64_t n_part,
-              torch::Tensor addend, bool wave_index) {
+              torch::Tensor addend, bool wave_index,
+              torch::Tensor packed, int64_t packed_depth) {
     CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
     const bool bf16 = xl.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(bf16 || xl.scalar_type() == torch::kFloat32,
@@ -756,6 +750,25 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
     const int32_t* e0_p = seg_e0.data_ptr<int32_t>();
     const int32_t* e1_p = seg_e1.data_ptr<int32_t>();
     const int32_t* sp_p = seg_part.data_ptr<int32_t>();
+    // packed operand (pack_rows(xl); a 0-element tensor means "none"):
+    // local columns are gathered from it, the result is the same bits
+    if (packed.numel()) {
+        CHECK_DEV(packed); CHECK_CONTIG(packed);
+        TORCH_CHECK(!bf16 && spmm_packable(F) && n_local > 0,
+                    "packed spmm expects fp32, F % 4 == 0, F <= 256 and "
+                    "at least one local row");
+        TORCH_CHECK(packed.scalar_type() == torch::kUInt8 &&
+                    packed.numel() == packed_buffer_bytes(n_local, F),
+                    "packed operand does not match xl (pack_rows(xl))");
+        launch_spmm_packed(
+            grid, block, s, (int)packed_depth, ind_p, xl.data_ptr<float>(),
+            reinterpret_cast<const float*>(xr_ptr),
+            packed.data_ptr<uint8_t>(), y.data_ptr<float>(), ss_p, ds_p,
+            sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(),
+            reinterpret_cast<const float*>(ad_ptr), n_seg, F, n_local);
+        combine();
+        return;
+    }
     auto run = [&](auto sw_tag, auto t_tag, auto ve_tag) {
         constexpr int SWC = decltype(sw_tag)::value;
         using TC = typename decltype(t_tag)::type;
@@ -863,7 +876,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("seg_e0"), pybind11::arg("seg_e1"),
           pybind11::arg("seg_part"), pybind11::arg("zero_rows"),
           pybind11::arg("part_ptr"), pybind11::arg("n_part"),
-          pybind11::arg("addend"), pybind11::arg("wave_index") = false);
+          pybind11::arg("addend"), pybind11::arg("wave_index") = false,
+          pybind11::arg("packed") = torch::Tensor(),
+          pybind11::arg("packed_depth") = 4);
+    m.def("pack_rows", &pack_rows,
+          "fixed-stride packed copy of a sparse fp32 [N,F] tensor for the "
+          "packed-gather SpMM (CDNA4)");
+    m.def("spmm_packable", &spmm_packable);
+    m.def("packed_meta_bytes", &packed_meta_bytes);
+    m.def("packed_row_stride", &packed_row_stride);
+    m.def("packed_buffer_bytes", &packed_buffer_bytes);
     m.def("colsum", &colsum,
           "deterministic column sum of a [N,F] fp32/bf16 matrix, fp32 "
           "accumulate (CDNA4)");

@@ -15,6 +15,7 @@ for bit; that is why it is opt-in.
 from __future__ import annotations
 
 import os
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -23,6 +24,10 @@ from torch import Tensor
 from ..ops.kernels import colsum
 
 _ones_cache: dict = {}
+
+# defaults of the two switches (docs/TUNING.md); the environment overrides
+SPMM_PACKED_DEFAULT = '1'
+AGG0_CACHE_DEFAULT = '1'
 
 
 def _ones_row(n: int, device, dtype) -> Tensor:
@@ -154,6 +159,49 @@ def fused_dual_linear(x, h, lin1: 'FastLinear', lin2: 'FastLinear') -> Tensor:
         lin2.bias.to(dt) if lin2.bias is not None else None)
 
 
+# --------------------------------------------------------------------------
+# reuse of a constant forward aggregate (layer 0 of full-graph training)
+#
+# The layer-0 aggregation reads the input features: no gradient flows into
+# them and, without remote rows, nothing stochastic enters the SpMM, so it
+# computes the same [num_inner, F0] tensor every epoch. The engine keeps the
+# last such result (one tensor, ~1 GB on the flagship) with the key it was
+# computed under; an in-place change of the features bumps their version
+# and misses. ADAQP_AGG0_CACHE=0 turns the reuse off. With several ranks the
+# quantized exchange is stochastic per epoch, so only the central rows of
+# the decomposed path would be constant; reusing those is not done.
+# --------------------------------------------------------------------------
+
+def _agg_cache_key(ctx, engine, x: Tensor, layer: int, is_train: bool):
+    """Cache key, or None when the aggregate may not be reused: the input
+    needs a gradient, the engine has remote rows or is tracing, or the
+    switch is off."""
+    if (ctx.needs_input_grad[0] or engine.graph.num_remote != 0
+            or engine.is_tracing
+            or os.environ.get('ADAQP_AGG0_CACHE', AGG0_CACHE_DEFAULT) == '0'):
+        return None
+    return (layer, x.data_ptr(), x._version, tuple(x.shape), x.dtype,
+            engine.compute_dtype, bool(is_train))
+
+
+def _agg_cache_get(engine, key) -> Optional[Tensor]:
+    if key is None:
+        return None
+    kept = getattr(engine, '_agg0_kept', None)
+    if kept is not None and kept[0] == key:
+        engine.agg0_hits = getattr(engine, 'agg0_hits', 0) + 1
+        return kept[2]
+    engine.agg0_misses = getattr(engine, 'agg0_misses', 0) + 1
+    return None
+
+
+def _agg_cache_put(engine, key, x: Tensor, h: Tensor) -> None:
+    # x is kept alive with the entry, so its data_ptr cannot be handed to
+    # another tensor while the key still names it
+    if key is not None:
+        engine._agg0_kept = (key, x, h)
+
+
 class _SageMeanFn(torch.autograd.Function):
     """The SAGE 'mean' layer, ``fc_self(x[:I]) + fc_neigh(mean_agg(x))``, as
     ONE autograd node. Forward is the unfused formulation call for call
@@ -168,16 +216,31 @@ class _SageMeanFn(torch.autograd.Function):
     cast backward. ``x`` is cast inside, as DistAgg does: when its dtype
     differs from the compute dtype (fp32 activations under bf16 autocast)
     the two input-grad terms are added in x's dtype, exactly as autograd
-    accumulated them, and the SpMM addend is not used."""
+    accumulated them, and the SpMM addend is not used.
+
+    ``pack``: the caller expects ``x`` to be mostly zeros (the output of
+    ReLU + dropout); the cast input is then packed once and the forward
+    SpMMs gather from the packed copy (same bits, fewer bytes per edge).
+    A tensor that does not qualify (``ops.kernels.packable``) is not
+    packed. The backward SpMM gathers a dense GEMM output and never is."""
 
     @staticmethod
     def forward(ctx, x: Tensor, w1: Tensor, w2: Tensor, b1: Tensor,
-                b2: Tensor, engine, layer: int, is_train: bool) -> Tensor:
+                b2: Tensor, engine, layer: int, is_train: bool,
+                pack: bool = False) -> Tensor:
         from ..ops.dist_agg import propagate
+        from ..ops.kernels import pack_rows
         from ..helpers import PropagationMode
         num_inner = engine.graph.num_inner
-        xa = x.to(engine.compute_dtype).contiguous()
-        h = propagate(engine, xa, layer, is_train, PropagationMode.Forward)
+        key = _agg_cache_key(ctx, engine, x, layer, is_train)
+        h = _agg_cache_get(engine, key)
+        if h is None:
+            xa = x.to(engine.compute_dtype).contiguous()
+            packed = pack_rows(xa) if pack else None
+            kw = {} if packed is None else {'packed': packed}
+            h = propagate(engine, xa, layer, is_train,
+                          PropagationMode.Forward, **kw)
+            _agg_cache_put(engine, key, x, h)
         xs = x[:num_inner].to(w1.dtype)
         ctx.engine, ctx.layer, ctx.in_dtype = engine, layer, x.dtype
         ctx.in_rows = x.shape[0]
@@ -207,15 +270,17 @@ class _SageMeanFn(torch.autograd.Function):
         gw2 = h.t() @ g if ctx.needs_input_grad[2] else None
         gb = bias_grad(g) if (ctx.needs_input_grad[3]
                            or ctx.needs_input_grad[4]) else None
-        return gx, gw1, gw2, gb, gb, None, None, None
+        return gx, gw1, gw2, gb, gb, None, None, None, None
 
 
 def sage_mean_layer(engine, x: Tensor, lin1: 'FastLinear', lin2: 'FastLinear',
-                    layer: int, is_train: bool) -> Tensor:
+                    layer: int, is_train: bool, pack: bool = False) -> Tensor:
     """lin1(x[:num_inner]) + lin2(mean aggregation of x) through
-    :class:`_SageMeanFn`; weight/bias casts mirror FastLinear.forward."""
+    :class:`_SageMeanFn`; weight/bias casts mirror FastLinear.forward.
+    ``pack``: hint that x is mostly zeros (see :class:`_SageMeanFn`)."""
     w1, w2, b1, b2 = lin1.weight, lin2.weight, lin1.bias, lin2.bias
     if torch.is_autocast_enabled('cuda') and x.is_cuda:
         dt = torch.get_autocast_dtype('cuda')
         w1, w2, b1, b2 = w1.to(dt), w2.to(dt), b1.to(dt), b2.to(dt)
-    return _SageMeanFn.apply(x, w1, w2, b1, b2, engine, layer, is_train)
+    return _SageMeanFn.apply(x, w1, w2, b1, b2, engine, layer, is_train,
+                             bool(pack))

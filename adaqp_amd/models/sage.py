@@ -15,8 +15,10 @@ from ..ops.dist_agg import dist_aggregate
 from .norm import FusedNormReluDropout, resolve_fused_norm
 import os
 
+from . import common as _common
 from .common import (FastLinear, fused_dual_linear, fused_dual_linear_ok,
                      sage_mean_layer)
+from ..ops.kernels import packable
 
 
 class DistSAGEConv(nn.Module):
@@ -35,7 +37,9 @@ class DistSAGEConv(nn.Module):
         if self.aggregator_type == 'mean':
             self.fc_self.reset_parameters()
 
-    def forward(self, engine, x: Tensor) -> Tensor:
+    def forward(self, engine, x: Tensor, pack: bool = False) -> Tensor:
+        # ``pack``: x is mostly zeros (DistSAGE.forward's hint), gather it
+        # from a packed copy in the forward SpMM.
         # gradients being recorded: the 'mean' layer is one autograd node
         # (same forward calls; fused input-grad add and a shared bias
         # grad in backward). The opt-in ADAQP_FUSED_SAGE path and the
@@ -48,7 +52,7 @@ class DistSAGEConv(nn.Module):
                 and x.shape[0] == engine.graph.num_inner
                 and os.environ.get('ADAQP_FUSED_SAGE') != '1'):
             return sage_mean_layer(engine, x, self.fc_self, self.fc_neigh,
-                                   self.layer, self.training)
+                                   self.layer, self.training, pack=pack)
         h_neigh = dist_aggregate(x, engine, self.layer, self.training)
         if self.aggregator_type == 'mean':
             x_self = x[:engine.graph.num_inner]
@@ -87,11 +91,30 @@ class DistSAGE(nn.Module):
                  for _ in range(num_layers - 1)]) if use_norm else None
         self.dropout = nn.Dropout(dropout)
 
+    def _pack_hint(self, engine, i: int, h: Tensor) -> bool:
+        """Whether layer i's forward SpMM should gather from packed rows.
+        Decided from what is known on the host, never from a device-side
+        count: the input of a layer > 0 in training is
+        dropout(relu(norm(.))), and with p >= 0.5 at most half of it is
+        non-zero in expectation (about a quarter with the ReLU), for the
+        nn.Dropout stack and the fused-norm stack alike. The tensor must
+        qualify once cast to the compute dtype (fp32, F % 4 == 0,
+        F <= 256). ADAQP_SPMM_PACKED=0/1 switches the whole thing."""
+        if os.environ.get('ADAQP_SPMM_PACKED',
+                          _common.SPMM_PACKED_DEFAULT) != '1':
+            return False
+        return (i > 0 and self.training and self.dropout.p >= 0.5
+                and engine.compute_dtype == torch.float32
+                and h.dtype == torch.float32 and packable(h))
+
     def forward(self, engine, feats: Tensor) -> Tensor:
         h = feats
         for i, conv in enumerate(self.convs):
             h = self.dropout(h) if i > 0 and not self.fused_norm else h
-            h = conv(engine, h)
+            if self._pack_hint(engine, i, h):
+                h = conv(engine, h, pack=True)
+            else:
+                h = conv(engine, h)
             if i < len(self.convs) - 1:
                 if self.fused_norm:
                     h = self.norms[i](h)

@@ -117,21 +117,29 @@ def _scales(engine, mode: PropagationMode) -> Tuple[Optional[Tensor], Optional[T
 
 
 def _agg(engine, view, x_local: Tensor, x_remote, src_scale, dst_scale,
-         out=None, addend=None) -> Tensor:
+         out=None, addend=None, packed=None) -> Tensor:
     """SpMM over one SpmmView. src_scale is the full [N] vector; dst_scale
     and the optional [num_inner, F] addend are sliced to the view's row
-    range."""
+    range. ``packed``: ``pack_rows(x_local)`` (the gather's source rows, so
+    the same handle serves every view)."""
     ds = (dst_scale[view.base:view.base + view.nrows]
           if dst_scale is not None else None)
     ad = (addend[view.base:view.base + view.nrows]
           if addend is not None else None)
+    if packed is not None:
+        return spmm(view, x_local, x_remote, src_scale, ds, out=out,
+                    addend=ad, packed=packed)
     return spmm(view, x_local, x_remote, src_scale, ds, out=out, addend=ad)
 
 
-def _addend_kw(addend) -> dict:
-    """_agg's ``addend`` keyword, passed only when there is one, so the
-    plain aggregation keeps the call signature it always had."""
-    return {} if addend is None else {'addend': addend}
+def _addend_kw(addend, packed=None) -> dict:
+    """_agg's ``addend`` and ``packed`` keywords, each passed only when
+    there is one, so the plain aggregation keeps the call signature it
+    always had."""
+    kw = {} if addend is None else {'addend': addend}
+    if packed is not None:
+        kw['packed'] = packed
+    return kw
 
 
 def _self_term(engine, x_local: Tensor, mode: PropagationMode) -> Tensor:
@@ -147,19 +155,21 @@ def _self_term(engine, x_local: Tensor, mode: PropagationMode) -> Tensor:
 # --------------------------------------------------------------------------
 
 def full_propagation(engine, x_local: Tensor, key: str, is_train: bool,
-                     mode: PropagationMode, addend=None) -> Tensor:
+                     mode: PropagationMode, addend=None,
+                     packed=None) -> Tensor:
     remote = _exchange(engine, x_local, key, is_train)
     src_scale, dst_scale, add_self = _scales(engine, mode)
     with engine.timer.record(f'{key}_full_aggregation'):
         y = _agg(engine, engine.full_view, x_local, remote, src_scale, dst_scale,
-                 **_addend_kw(addend))
+                 **_addend_kw(addend, packed))
         if add_self:
             y = y + _self_term(engine, x_local, mode)
     return y
 
 
 def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
-                           mode: PropagationMode, addend=None) -> Tensor:
+                           mode: PropagationMode, addend=None,
+                           packed=None) -> Tensor:
     """Central aggregation (default stream) overlapped with
     quant->all_to_all->dequant (comm stream).
 
@@ -193,7 +203,7 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
         # the transport can block the host
         with engine.timer.record(f'{key}_central_aggregation'):
             _agg(engine, engine.central_view, x_local, None, src_scale,
-                 dst_scale, out=y[:C], **_addend_kw(addend))
+                 dst_scale, out=y[:C], **_addend_kw(addend, packed))
         with torch.cuda.stream(engine.comm_stream):
             remote = _exchange_finish(engine, staged, key)
             engine.remote_ready.record(engine.comm_stream)
@@ -201,15 +211,15 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
         remote.record_stream(torch.cuda.current_stream())
         with engine.timer.record(f'{key}_marginal_aggregation'):
             _agg(engine, engine.marginal_view, x_local, remote, src_scale,
-                 dst_scale, out=y[C:], **_addend_kw(addend))
+                 dst_scale, out=y[C:], **_addend_kw(addend, packed))
     else:
         remote = _exchange(engine, x_local, key, is_train)
         with engine.timer.record(f'{key}_central_aggregation'):
             y_c = _agg(engine, engine.central_view, x_local, None, src_scale,
-                       dst_scale, **_addend_kw(addend))
+                       dst_scale, **_addend_kw(addend, packed))
         with engine.timer.record(f'{key}_marginal_aggregation'):
             y_m = _agg(engine, engine.marginal_view, x_local, remote,
-                       src_scale, dst_scale, **_addend_kw(addend))
+                       src_scale, dst_scale, **_addend_kw(addend, packed))
         y = torch.cat([y_c, y_m], dim=0)
     if add_self:
         y = y + _self_term(engine, x_local, mode)
@@ -217,16 +227,19 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
 
 
 def propagate(engine, x_local: Tensor, layer: int, is_train: bool,
-              mode: PropagationMode, addend=None) -> Tensor:
+              mode: PropagationMode, addend=None, packed=None) -> Tensor:
     """``addend`` ([num_inner, F], the result's dtype): added to the
-    aggregation in the SpMM epilogue, before any self term."""
+    aggregation in the SpMM epilogue, before any self term.
+    ``packed``: ``pack_rows(x_local)``; the SpMMs gather local rows from
+    it, the exchange still reads the dense ``x_local``."""
     key = (f'forward{layer}' if mode == PropagationMode.Forward
            else f'backward{layer}')
+    kw = {} if packed is None else {'packed': packed}
     if engine.use_parallel:
         return decomposed_propagation(engine, x_local, key, is_train, mode,
-                                      addend=addend)
+                                      addend=addend, **kw)
     return full_propagation(engine, x_local, key, is_train, mode,
-                            addend=addend)
+                            addend=addend, **kw)
 
 
 # --------------------------------------------------------------------------

@@ -119,6 +119,8 @@ SEG_EDGES = int(_os.environ.get('ADAQP_SEG_EDGES', '256'))
 # so it stays behind this switch. ADAQP_SPMM_WAVE_INDEX=1 turns it on
 # (read once, here).
 WAVE_INDEX = _os.environ.get('ADAQP_SPMM_WAVE_INDEX', '0') == '1'
+# row fetches in flight per lane in the packed-gather SpMM (4 or 8)
+PACKED_DEPTH = int(_os.environ.get('ADAQP_SPMM_PACKED_DEPTH', '4'))
 
 
 def _auto_seg(num_edges: int, num_rows: int) -> int:
@@ -229,10 +231,53 @@ class SpmmView:
         return self
 
 
+PACK_MAX_FEATS = 256
+
+
+def packable(x: Tensor) -> bool:
+    """True if ``x`` can be the packed operand of :func:`spmm`: a GPU fp32
+    contiguous [N, F] tensor with at least one row, F % 4 == 0 and
+    F <= 256. Everything else (bf16, other F, CPU tensors) runs the dense
+    SpMM kernel."""
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+            and x.is_contiguous() and x.shape[0] > 0
+            and 0 < x.shape[1] <= PACK_MAX_FEATS and x.shape[1] % 4 == 0)
+
+
+class PackedRows:
+    """Packed copy of a sparse [N, F] fp32 tensor (csrc/spmm_packed.hip has
+    the layout): per row ``F/4`` 16-bit words (8-bit value offset, 4-bit
+    presence mask, bit 15 = overflow row) padded to ``meta_bytes``, then
+    up to ``F/2`` kept fp32 values; rows are ``stride`` bytes apart in the
+    uint8 buffer ``buf``. Rows with more than F/2 non-zero bit patterns
+    are overflow rows and are read from the dense tensor."""
+
+    def __init__(self, buf: Tensor, rows: int, feats: int):
+        C = native()
+        self.buf, self.rows, self.feats = buf, rows, feats
+        self.meta_bytes = int(C.packed_meta_bytes(feats))
+        self.stride = int(C.packed_row_stride(feats))
+
+    def matches(self, x: Tensor) -> bool:
+        return (packable(x) and x.shape[0] == self.rows
+                and x.shape[1] == self.feats and x.device == self.buf.device)
+
+
+def pack_rows(x: Tensor) -> Optional[PackedRows]:
+    """One pass of the native pack kernel over ``x``; ``None`` when ``x``
+    does not qualify (see :func:`packable`), which callers pass on to
+    :func:`spmm` as "no packed operand"."""
+    if not packable(x):
+        return None
+    return PackedRows(native().pack_rows(x), x.shape[0], x.shape[1])
+
+
 def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
          src_scale: Optional[Tensor], dst_scale: Optional[Tensor],
          out: Optional[Tensor] = None, addend: Optional[Tensor] = None,
-         wave_index: Optional[bool] = None) -> Tensor:
+         wave_index: Optional[bool] = None,
+         packed: Optional[PackedRows] = None,
+         packed_depth: Optional[int] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
     Columns < len(x_local) read x_local; the rest read x_remote (the
@@ -245,6 +290,11 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
     result is ``spmm(...) + addend`` bit for bit, added in the kernel's
     epilogue instead of a separate pass.
     ``wave_index``: which SW == 64 kernel runs (None = WAVE_INDEX).
+    ``packed``: ``pack_rows(x_local)``; local columns are then gathered
+    from the packed copy (remote columns and overflow rows from the dense
+    tensors), same result bit for bit. Ignored on the CPU.
+    ``packed_depth``: row fetches in flight per lane in that kernel
+    (None = PACKED_DEPTH).
     """
     indptr, indices, num_rows = view.indptr, view.indices, view.nrows
     if not x_local.is_cuda and view.col_blocked:
@@ -261,6 +311,9 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
         if addend is not None:
             assert (addend.is_contiguous() and addend.dtype == out.dtype
                     and addend.shape == out.shape)
+        if packed is not None:
+            assert packed.matches(x_local), \
+                'packed operand was not made from x_local'
         native().spmm_csr(indices, x_local,
                           x_remote if x_remote is not None else empty, out,
                           src_scale if src_scale is not None else empty,
@@ -270,7 +323,10 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
                           view.n_part,
                           addend if addend is not None else empty,
                           bool(WAVE_INDEX if wave_index is None
-                               else wave_index))
+                               else wave_index),
+                          packed.buf if packed is not None else empty,
+                          int(PACKED_DEPTH if packed_depth is None
+                              else packed_depth))
         return out
     x = (torch.cat([x_local, x_remote], dim=0)
          if x_remote is not None and x_remote.numel() else x_local)

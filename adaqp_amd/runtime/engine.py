@@ -53,6 +53,11 @@ class GraphEngine:
                            mode='events')
         self.is_tracing = False
         self.traced: Dict[str, Tensor] = {}      # key -> accumulated per-send-node variance proxy
+        # reuse of the constant layer-0 forward aggregate (models/common.py):
+        # (key, input, result) of the last one kept, and hit/miss counters
+        self._agg0_kept = None
+        self.agg0_hits = 0
+        self.agg0_misses = 0
 
         g = self.graph
         din = g.in_deg.clamp(min=1.0)

@@ -22,7 +22,8 @@ setup(
             name='adaqp_amd._C',
             sources=['adaqp_amd/csrc/kernels.hip',
                      'adaqp_amd/csrc/norm_act.hip',
-                     'adaqp_amd/csrc/colsum.hip'],
+                     'adaqp_amd/csrc/colsum.hip',
+                     'adaqp_amd/csrc/spmm_packed.hip'],
             extra_compile_args={'cxx': ['-O3'],
                                 'nvcc': ['-O3', '--offload-arch=gfx950']},
         )

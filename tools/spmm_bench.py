@@ -7,7 +7,13 @@ spmm_csr kernel; prints effective gather TB/s.
 1 = wave-uniform index kernel; default: the library's). Both
 (``--wave-index 0,1``) are alternated call by call and each is reported
 as median (min..max) of per-call device-event times, after checking that
-they produce the same bits."""
+they produce the same bits.
+
+``--packed 0,1`` does the same for the packed-gather kernel against the
+dense one (fp32, F % 4 == 0, F <= 256), once per ``--density``: the input
+is synthetic, zeros placed i.i.d. per element, and the pack kernel is timed
+on its own. ``--packed-depth 4,8`` adds one packed variant per number of
+row fetches in flight."""
 import argparse
 import os
 import statistics
@@ -48,6 +54,14 @@ def main():
     p.add_argument('--wave-index', type=str, default=None,
                    help='SW == 64 kernel: 0 or 1; "0,1" alternates them call '
                         'by call')
+    p.add_argument('--packed', type=str, default=None,
+                   help='"0,1": dense and packed-gather kernel alternated '
+                        'call by call, per --density')
+    p.add_argument('--density', type=str, default='0.25,0.5,1.0',
+                   help='fractions of non-zero elements for --packed')
+    p.add_argument('--packed-depth', type=str, default='4',
+                   help='row fetches in flight in the packed kernel (4, 8 '
+                        'or "4,8")')
     args = p.parse_args()
     assert torch.cuda.is_available()
     from adaqp_amd.ops.kernels import SpmmView, spmm, native
@@ -63,6 +77,10 @@ def main():
     gather_bytes = E * (args.F * x.element_size() + 12)
     head = (f'rows={args.rows} E={E} F={args.F} {args.dtype} '
             f'cb={args.col_block}')
+
+    if args.packed is not None:
+        packed_bench(args, view, x, src, dst, E, head)
+        return
 
     if args.wave_index is None or ',' not in args.wave_index:
         wi = None if args.wave_index is None else bool(int(args.wave_index))
@@ -103,6 +121,69 @@ def main():
         print(f'  wave-index {m}: {med:.3f} ms ({min(t):.3f}..{max(t):.3f}), '
               f'apparent gather {gather_bytes/(med*1e-3)/1e12:.2f} TB/s')
     sys.stdout.flush()
+
+
+def _timed(fn):
+    a = torch.cuda.Event(enable_timing=True)
+    b = torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def _fmt(t):
+    return f'{statistics.median(t):.3f} ms ({min(t):.3f}..{max(t):.3f})'
+
+
+def packed_bench(args, view, x, src, dst, E, head):
+    from adaqp_amd.ops.kernels import pack_rows, spmm
+    assert x.dtype == torch.float32, '--packed is fp32 only'
+    want = [int(m) for m in args.packed.split(',')]
+    depths = [int(d) for d in args.packed_depth.split(',')]
+    # variants: None = dense kernel, d = packed kernel with d fetches in flight
+    variants = ([None] if 0 in want else []) + (depths if 1 in want else [])
+    gen = torch.Generator(device=x.device).manual_seed(7)
+    for dens in [float(d) for d in args.density.split(',')]:
+        keep = torch.rand(x.shape, device=x.device, generator=gen) < dens
+        xd = (x * keep).contiguous()
+        del keep
+        nnz = (xd != 0).sum(1)
+        ovf = float((nnz > args.F // 2).float().mean())
+        tp = []
+        for i in range(3 + args.iters):
+            t, pk = _timed(lambda: pack_rows(xd))
+            if i >= 3:
+                tp.append(t)
+        assert pk is not None
+        outs = {}
+        for _ in range(3):
+            for v in variants:
+                outs[v] = spmm(view, xd, None, src, dst,
+                               packed=None if v is None else pk,
+                               packed_depth=v)
+        torch.cuda.synchronize()
+        same = all(torch.equal(outs[variants[0]], outs[v])
+                   for v in variants[1:])
+        print(f'{head} density={dens} (overflow rows {ovf:.3f}): outputs of '
+              f'{["dense" if v is None else f"packed/{v}" for v in variants]}'
+              f' bit-identical: {same}')
+        print(f'  pack kernel: {_fmt(tp)}, '
+              f'{(xd.numel() * 4 + pk.buf.numel()) / (statistics.median(tp) * 1e-3) / 1e12:.2f}'
+              f' TB/s read + written (upper bound on bytes)')
+        times = {v: [] for v in variants}
+        for _ in range(args.iters):
+            for v in variants:
+                t, _ = _timed(lambda: spmm(view, xd, None, src, dst,
+                                           packed=None if v is None else pk,
+                                           packed_depth=v))
+                times[v].append(t)
+        for v in variants:
+            name = 'dense' if v is None else f'packed, {v} in flight'
+            print(f'  {name}: {_fmt(times[v])}')
+        sys.stdout.flush()
+        del xd, pk, outs
 
 
 if __name__ == '__main__':
