@@ -838,6 +838,18 @@ int64_t norm_act_max_feats();
 // colsum.hip
 torch::Tensor colsum(torch::Tensor g);
 
+// masked_loss.hip
+std::vector<torch::Tensor> masked_loss_fwd(torch::Tensor logits,
+                                           torch::Tensor labels,
+                                           torch::Tensor mask,
+                                           bool multilabel);
+torch::Tensor masked_loss_bwd(torch::Tensor logits, torch::Tensor labels,
+                              torch::Tensor mask, torch::Tensor stats,
+                              torch::Tensor g, bool multilabel);
+int64_t masked_loss_max_blocks();
+int64_t masked_loss_max_classes();
+int64_t masked_loss_rows_per_block(int64_t C);
+
 void fused_dual_gemm_bf16(torch::Tensor a1, torch::Tensor a2,
                           torch::Tensor w1t, torch::Tensor w2t,
                           torch::Tensor bias, torch::Tensor out) {
@@ -899,4 +911,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.attr("NORM_ACT_BWD_MAX_BLOCKS") = norm_act_bwd_max_blocks();
     m.attr("NORM_ACT_WAVES_PER_BLOCK") = norm_act_waves_per_block();
     m.attr("NORM_ACT_MAX_FEATS") = norm_act_max_feats();
+    m.def("masked_loss_fwd", &masked_loss_fwd,
+          "masked softmax-CE / BCE-with-logits sum; returns {loss, stats} "
+          "(CDNA4)");
+    m.def("masked_loss_bwd", &masked_loss_bwd,
+          "gradient of masked_loss_fwd with respect to the logits (CDNA4)");
+    m.def("masked_loss_rows_per_block", &masked_loss_rows_per_block,
+          "rows a block handles per trip of its row loop, for C classes");
+    m.attr("MASKED_LOSS_MAX_BLOCKS") = masked_loss_max_blocks();
+    m.attr("MASKED_LOSS_MAX_CLASSES") = masked_loss_max_classes();
 }

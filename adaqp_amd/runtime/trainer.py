@@ -57,6 +57,8 @@ class Trainer:
                 rt[k] = v
         if getattr(args, 'fused_norm', False):     # CLI overrides the config
             self.cfg['model']['fused_norm'] = True
+        if getattr(args, 'fused_loss', False):
+            rt['fused_loss'] = True
         self.mode = RunMode(args.mode)
         self.model_type = MODEL_MAP[args.model_name]
         self.comm = Communicator(backend=getattr(args, 'backend', None),
@@ -181,7 +183,8 @@ class Trainer:
                 self.assigner.reassign()
             t0 = time.perf_counter()
             loss = train_epoch(self.engine, self.model, self.optimizer, gc,
-                               self.multilabel)
+                               self.multilabel,
+                               fused_loss=rt.get('fused_loss'))
             if self.engine.device.type == 'cuda':
                 torch.cuda.synchronize()
             self.epoch_times.append(time.perf_counter() - t0)

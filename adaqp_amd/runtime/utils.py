@@ -8,13 +8,14 @@ correctly scaled — same convention here.
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 import torch.nn.functional as F
 from torch import Tensor
 
 from ..comm.communicator import Communicator
+from ..ops.loss import masked_loss, resolve_fused_loss
 
 
 def global_train_count(engine) -> Tensor:
@@ -24,7 +25,13 @@ def global_train_count(engine) -> Tensor:
 
 
 def compute_loss(logits: Tensor, labels: Tensor, mask: Tensor,
-                 multilabel: bool, global_count: Tensor) -> Tensor:
+                 multilabel: bool, global_count: Tensor,
+                 fused: Optional[bool] = None) -> Tensor:
+    """Masked training loss over the global train count. ``fused`` picks
+    the one-op ``ops.loss.masked_loss`` (None: env ``ADAQP_FUSED_LOSS=1``),
+    which takes fp32 or bf16 logits and never syncs the host."""
+    if resolve_fused_loss(fused):
+        return masked_loss(logits, labels, mask, multilabel) / global_count
     if multilabel:
         raw = F.binary_cross_entropy_with_logits(
             logits[mask], labels[mask].float(), reduction='sum') / logits.shape[1]
@@ -41,15 +48,17 @@ def _autocast(engine):
 
 
 def train_epoch(engine, model, optimizer, global_count: Tensor,
-                multilabel: bool) -> Tensor:
+                multilabel: bool, fused_loss: Optional[bool] = None) -> Tensor:
     comm = Communicator.ctx
+    fused = resolve_fused_loss(fused_loss)
     model.train()
     optimizer.zero_grad(set_to_none=False)
     with _autocast(engine):
         logits = model(engine, engine.graph.feats)
-    logits = logits.float()
+    if not fused:       # the fused loss widens the model's dtype in registers
+        logits = logits.float()
     loss = compute_loss(logits, engine.graph.labels, engine.graph.train_mask,
-                        multilabel, global_count)
+                        multilabel, global_count, fused=fused)
     loss.backward()
     with engine.timer.record('grad_reduce'):
         comm.flat_all_reduce_grads(model.parameters())

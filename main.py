@@ -54,6 +54,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help='fused LayerNorm+ReLU+dropout between layers '
                         '(overrides the config; ADAQP_FUSED_NORM=1 is the '
                         'env switch when neither sets it)')
+    p.add_argument('--fused_loss', action='store_true',
+                   help='one-op masked training loss (sets runtime.fused_loss; '
+                        'ADAQP_FUSED_LOSS=1 is the env switch when neither '
+                        'sets it)')
     return p
 
 

@@ -23,7 +23,8 @@ setup(
             sources=['adaqp_amd/csrc/kernels.hip',
                      'adaqp_amd/csrc/norm_act.hip',
                      'adaqp_amd/csrc/colsum.hip',
-                     'adaqp_amd/csrc/spmm_packed.hip'],
+                     'adaqp_amd/csrc/spmm_packed.hip',
+                     'adaqp_amd/csrc/masked_loss.hip'],
             extra_compile_args={'cxx': ['-O3'],
                                 'nvcc': ['-O3', '--offload-arch=gfx950']},
         )
