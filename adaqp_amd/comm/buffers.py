@@ -50,6 +50,11 @@ class SidePlan:
     node_splits: List[int]        # per peer node counts
     total_bytes: int
     total_nodes: int
+    # recv side: int32 [max row + 1, 4], row r = {wire byte offset (the
+    # unsigned 32-bit value's bits), params slot, bits, 0} of remote-block
+    # row r, all zero (bits 0) for a row no peer sends. None when it was not
+    # asked for or total_bytes does not fit an unsigned 32-bit offset.
+    row_tab: Optional[Tensor] = None
 
     @property
     def param_splits(self) -> List[int]:
@@ -59,6 +64,8 @@ class SidePlan:
         self.rows = {b: t.to(device) for b, t in self.rows.items()}
         self.pos = {b: t.to(device) for b, t in self.pos.items()}
         self.off = {b: t.to(device) for b, t in self.off.items()}
+        if self.row_tab is not None:
+            self.row_tab = self.row_tab.to(device)
         return self
 
 
@@ -75,9 +82,28 @@ class KeyPlan:
         return self
 
 
+def _row_table(rows: Dict[int, Tensor], pos: Dict[int, Tensor],
+               off: Dict[int, Tensor], total_bytes: int) -> Optional[Tensor]:
+    """The per-row view of a layout (SidePlan.row_tab): the same
+    rows/pos/off, indexed by row instead of grouped by bit width."""
+    if total_bytes >= 2 ** 32:
+        return None
+    n = max([int(r.max()) + 1 for r in rows.values() if r.numel()], default=0)
+    tab = torch.zeros(n, 4, dtype=torch.int64)
+    for b in BITS_SET:
+        tab[rows[b], 0] = off[b]
+        tab[rows[b], 1] = pos[b]
+        tab[rows[b], 2] = b
+    tab[:, 0] -= (tab[:, 0] >= 2 ** 31).to(torch.int64) * 2 ** 32
+    return tab.to(torch.int32)
+
+
 def _layout(bits_per_peer: List[Optional[Tensor]],
-            rows_per_peer: List[Optional[Tensor]], F: int) -> SidePlan:
-    """Build one side's layout from per-peer bit vectors (agreed order)."""
+            rows_per_peer: List[Optional[Tensor]], F: int,
+            row_tab: bool = True) -> SidePlan:
+    """Build one side's layout from per-peer bit vectors (agreed order).
+    ``row_tab``: also build the per-row table (the recv side's rows are
+    remote-block rows, each at most once; a send side has no use for it)."""
     rows = {b: [] for b in BITS_SET}
     pos = {b: [] for b in BITS_SET}
     off = {b: [] for b in BITS_SET}
@@ -110,8 +136,10 @@ def _layout(bits_per_peer: List[Optional[Tensor]],
         node_splits.append(n)
     cat = lambda d: {b: (torch.cat(v) if v else torch.empty(0, dtype=torch.int64))
                      for b, v in d.items()}
-    return SidePlan(F, cat(rows), cat(pos), cat(off), byte_splits, node_splits,
-                    b_cursor, p_cursor)
+    rows, pos, off = cat(rows), cat(pos), cat(off)
+    tab = _row_table(rows, pos, off, b_cursor) if row_tab else None
+    return SidePlan(F, rows, pos, off, byte_splits, node_splits,
+                    b_cursor, p_cursor, tab)
 
 
 def exchange_bits(comm: Communicator, graph: LocalGraph,
@@ -150,7 +178,7 @@ def build_key_plan(comm: Communicator, graph: LocalGraph, F: int,
         n = graph.recv_splits[p]
         recv_rows_l.append(torch.arange(base, base + n, dtype=torch.int64) if n else None)
         base += n
-    plan = KeyPlan(F, _layout(send_bits_l, send_rows_l, F),
+    plan = KeyPlan(F, _layout(send_bits_l, send_rows_l, F, row_tab=False),
                    _layout(recv_bits_l, recv_rows_l, F))
     if device is not None:
         plan.to(device)

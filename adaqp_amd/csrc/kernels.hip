@@ -602,6 +602,16 @@ void launch_spmm_packed(
     const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
     const int32_t* seg_e1, const int32_t* seg_part, float* part,
     const float* addend, int64_t n_seg, int64_t F, int64_t n_local);
+// spmm_quant.hip
+int64_t quant_pad_bytes();
+torch::Tensor quant_row_desc(torch::Tensor tab, torch::Tensor params);
+void launch_spmm_quant(
+    dim3 grid, dim3 block, hipStream_t s, int sw, int ve,
+    const int32_t* indices, const float* xl, torch::Tensor payload,
+    torch::Tensor desc, float* y, const float* src_scale,
+    const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
+    const int32_t* seg_e1, const int32_t* seg_part, float* part,
+    const float* addend, int64_t n_seg, int64_t F, int64_t n_local);
 
 static inline hipStream_t cur_stream() {
     return at::cuda::getCurrentHIPStream().stream();
@@ -669,7 +679,8 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
               torch::Tensor seg_part, torch::Tensor zero_rows,
               torch::Tensor part_ptr, int64_t n_part,
               torch::Tensor addend, bool wave_index,
-              torch::Tensor packed, int64_t packed_depth) {
+              torch::Tensor packed, int64_t packed_depth,
+              torch::Tensor q_payload, torch::Tensor q_desc) {
     CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
     const bool bf16 = xl.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(bf16 || xl.scalar_type() == torch::kFloat32,
@@ -750,6 +761,21 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
     const int32_t* e0_p = seg_e0.data_ptr<int32_t>();
     const int32_t* e1_p = seg_e1.data_ptr<int32_t>();
     const int32_t* sp_p = seg_part.data_ptr<int32_t>();
+    // quantized remote operand (the wire payload and quant_row_desc's block;
+    // a 0-element q_desc means "none"): remote columns are gathered from the
+    // payload, the result is the same bits as with the unpacked block as xr.
+    // It takes precedence over a packed operand, which is then not read.
+    if (q_desc.defined() && q_desc.numel()) {
+        TORCH_CHECK(!bf16 && !xr.numel(),
+                    "quantized spmm expects fp32 and no dense remote block");
+        launch_spmm_quant(
+            grid, block, s, sw, ve, ind_p, xl.data_ptr<float>(), q_payload,
+            q_desc, y.data_ptr<float>(), ss_p, ds_p, sr_p, e0_p, e1_p, sp_p,
+            part.data_ptr<float>(), reinterpret_cast<const float*>(ad_ptr),
+            n_seg, F, n_local);
+        combine();
+        return;
+    }
     // packed operand (pack_rows(xl); a 0-element tensor means "none"):
     // local columns are gathered from it, the result is the same bits
     if (packed.numel()) {
@@ -890,7 +916,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("part_ptr"), pybind11::arg("n_part"),
           pybind11::arg("addend"), pybind11::arg("wave_index") = false,
           pybind11::arg("packed") = torch::Tensor(),
-          pybind11::arg("packed_depth") = 4);
+          pybind11::arg("packed_depth") = 4,
+          pybind11::arg("q_payload") = torch::Tensor(),
+          pybind11::arg("q_desc") = torch::Tensor());
+    m.def("quant_row_desc", &quant_row_desc,
+          "per-remote-row {offset, bits, inv, rmin} descriptors of one "
+          "quantized exchange, for the quantized-gather SpMM (CDNA4)");
+    m.attr("QUANT_PAD") = quant_pad_bytes();
     m.def("pack_rows", &pack_rows,
           "fixed-stride packed copy of a sparse fp32 [N,F] tensor for the "
           "packed-gather SpMM (CDNA4)");

@@ -26,7 +26,8 @@ from torch import Tensor
 
 from ..helpers import BitType, DistGNNType, PropagationMode
 from ..comm.communicator import Communicator
-from .kernels import mixed_quantize, mixed_dequantize, spmm
+from .kernels import (mixed_quantize, mixed_dequantize, spmm, QuantRemote,
+                      resolve_fused_dequant)
 
 
 # --------------------------------------------------------------------------
@@ -54,8 +55,20 @@ def _exchange_start(engine, x_local: Tensor, key: str, quant: bool):
     return ('fp', send, None, x_local.dtype)
 
 
-def _exchange_finish(engine, staged, key: str) -> Tensor:
-    """Transport + consumer-side kernels (dequant/scatter)."""
+def _fused_dequant(engine, x_local: Tensor, key: str, quant: bool) -> bool:
+    """True if this exchange hands the SpMM the wire buffer instead of a
+    dequantized block: the engine's switch is on, the exchange is
+    quantized, fp32, on the GPU, and the plan has its per-row table."""
+    return (quant and x_local.is_cuda and x_local.dtype == torch.float32
+            and resolve_fused_dequant(getattr(engine, 'fused_dequant', None))
+            and engine.plans[key].recv.row_tab is not None)
+
+
+def _exchange_finish(engine, staged, key: str, fused: bool = False):
+    """Transport + consumer-side kernels (dequant/scatter). ``fused``
+    (quantized exchanges only): return a :class:`QuantRemote` over the
+    received wire buffer; the only consumer-side kernel is then the one
+    that writes its row descriptors."""
     comm = Communicator.ctx
     g = engine.graph
     kind, a, b, dtype = staged
@@ -65,8 +78,12 @@ def _exchange_finish(engine, staged, key: str) -> Tensor:
         return recv
     plan = engine.plans[key]
     payload, params = a, b
-    recv_payload = torch.empty(plan.recv.total_bytes, dtype=torch.uint8,
-                               device=payload.device)
+    # fused: the collective gets a view of the exact wire length of a
+    # buffer with the spare bytes the gather's window loads need
+    recv_payload = (QuantRemote.wire_buffer(plan.recv.total_bytes,
+                                            payload.device) if fused else
+                    torch.empty(plan.recv.total_bytes, dtype=torch.uint8,
+                                device=payload.device))
     recv_params = torch.empty(2 * plan.recv.total_nodes, dtype=torch.bfloat16,
                               device=payload.device)
     with engine.timer.record(f'{key}_exchange'):
@@ -74,6 +91,13 @@ def _exchange_finish(engine, staged, key: str) -> Tensor:
                           plan.recv.byte_splits, plan.send.byte_splits)
         comm.all_to_all_v(recv_params, params,
                           plan.recv.param_splits, plan.send.param_splits)
+    if fused:
+        remote = QuantRemote(recv_payload, recv_params, plan.recv, plan.F,
+                             rows=g.num_remote)
+        with engine.timer.record(f'{key}_dequant'):
+            if remote.rows:
+                remote.descriptors()
+        return remote
     out = torch.empty(g.num_remote, plan.F, dtype=dtype,
                       device=payload.device)
     with engine.timer.record(f'{key}_dequant'):
@@ -157,7 +181,13 @@ def _self_term(engine, x_local: Tensor, mode: PropagationMode) -> Tensor:
 def full_propagation(engine, x_local: Tensor, key: str, is_train: bool,
                      mode: PropagationMode, addend=None,
                      packed=None) -> Tensor:
-    remote = _exchange(engine, x_local, key, is_train)
+    quant = engine.bit_type == BitType.QUANT and is_train
+    if _fused_dequant(engine, x_local, key, quant):
+        remote = _exchange_finish(
+            engine, _exchange_start(engine, x_local, key, True), key,
+            fused=True)
+    else:
+        remote = _exchange(engine, x_local, key, is_train)
     src_scale, dst_scale, add_self = _scales(engine, mode)
     with engine.timer.record(f'{key}_full_aggregation'):
         y = _agg(engine, engine.full_view, x_local, remote, src_scale, dst_scale,
@@ -204,8 +234,13 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
         with engine.timer.record(f'{key}_central_aggregation'):
             _agg(engine, engine.central_view, x_local, None, src_scale,
                  dst_scale, out=y[:C], **_addend_kw(addend, packed))
+        # fused dequant: `remote` is a QuantRemote (the wire buffer and its
+        # row descriptors); the marginal SpMM gathers from it, and a packed
+        # operand is ignored for that view (ops/kernels.py::spmm)
+        fused_kw = ({'fused': True}
+                    if _fused_dequant(engine, x_local, key, quant) else {})
         with torch.cuda.stream(engine.comm_stream):
-            remote = _exchange_finish(engine, staged, key)
+            remote = _exchange_finish(engine, staged, key, **fused_kw)
             engine.remote_ready.record(engine.comm_stream)
         torch.cuda.current_stream().wait_event(engine.remote_ready)
         remote.record_stream(torch.cuda.current_stream())

@@ -152,6 +152,9 @@ class SpmmView:
         self.indptr = indptr
         self.base = int(base)
         self.nrows = int(nrows)
+        # largest column any edge names (-1: no edges); spmm checks it
+        # against the rows a quantized remote operand describes
+        self.max_col = int(indices.max()) if indices.numel() else -1
         self.col_blocked = col_block > 0 and indices.numel() > 0
         SEG = _auto_seg(int(indices.numel()), nrows)
         indptr_c = indptr.cpu()
@@ -272,7 +275,87 @@ def pack_rows(x: Tensor) -> Optional[PackedRows]:
     return PackedRows(native().pack_rows(x), x.shape[0], x.shape[1])
 
 
-def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
+def resolve_fused_dequant(flag: Optional[bool]) -> bool:
+    """``None`` -> on iff env ``ADAQP_FUSED_DEQUANT=1``; an explicit bool
+    wins. (``GraphEngine.fused_dequant`` is the flag; ops/dist_agg.py
+    resolves it at every propagation.)"""
+    if flag is None:
+        return _os.environ.get('ADAQP_FUSED_DEQUANT') == '1'
+    return bool(flag)
+
+
+class QuantRemote:
+    """The remote block of one quantized exchange, left in wire form: the
+    received ``payload`` (uint8 [plan.total_bytes]) and ``params`` (bf16
+    [2 * plan.total_nodes]) with the recv-side ``plan``. :func:`spmm` takes
+    it in place of the dense ``x_remote`` and, for GPU fp32, gathers remote
+    columns straight from the payload (csrc/spmm_quant.hip): same result
+    bit for bit as with ``dequantize()``'s block, except that a row the
+    plan does not cover reads as zero instead of being left unwritten.
+    ``rows``: rows of the remote block (default: the plan's table).
+
+    The gather's loads reach up to QUANT_PAD bytes past the wire length,
+    so on the GPU the payload has to start 4-byte aligned and have that
+    many spare bytes behind it in its storage (``wire_buffer`` allocates
+    such a tensor); one that does not is copied into one that does."""
+
+    def __init__(self, payload: Tensor, params: Tensor, plan: SidePlan,
+                 F: int, rows: Optional[int] = None):
+        assert plan.F == F and payload.dtype == torch.uint8
+        assert payload.numel() == plan.total_bytes
+        assert params.numel() == 2 * plan.total_nodes
+        if rows is None:
+            rows = (plan.row_tab.shape[0] if plan.row_tab is not None else
+                    max([int(r.max()) + 1 for r in plan.rows.values()
+                         if r.numel()], default=0))
+        self.params, self.plan, self.F, self.rows = params, plan, F, int(rows)
+        if payload.is_cuda and plan.row_tab is not None:
+            pad = int(native().QUANT_PAD)
+            spare = (payload.untyped_storage().nbytes()
+                     - payload.storage_offset() - payload.numel())
+            if (not payload.is_contiguous() or payload.data_ptr() % 4
+                    or spare < pad):
+                buf = self.wire_buffer(payload.numel(), payload.device)
+                payload = buf.copy_(payload)
+        self.payload = payload
+        self._desc: Optional[Tensor] = None
+
+    @staticmethod
+    def wire_buffer(nbytes: int, device) -> Tensor:
+        """uint8 [nbytes] view of an allocation with the spare bytes the
+        gather needs behind it."""
+        pad = int(native().QUANT_PAD) if torch.device(device).type == 'cuda' else 0
+        return torch.empty(nbytes + pad, dtype=torch.uint8,
+                           device=device)[:nbytes]
+
+    def fusable(self, x_local: Tensor) -> bool:
+        """True if :func:`spmm` runs the quantized-gather kernel for this
+        operand: GPU, fp32, a per-row table in the plan, and at least one
+        local and one remote row. Everything else dequantizes."""
+        return (x_local.is_cuda and x_local.dtype == torch.float32
+                and self.plan.row_tab is not None
+                and x_local.shape[0] > 0 and self.rows > 0)
+
+    def descriptors(self) -> Tensor:
+        """int32 [rows, 4] {payload byte offset, bits, inv, rmin} per
+        remote row, built once on the current stream."""
+        if self._desc is None:
+            assert self.plan.row_tab.shape[0] == self.rows
+            self._desc = native().quant_row_desc(self.plan.row_tab, self.params)
+        return self._desc
+
+    def dequantize(self, dtype=torch.float32) -> Tensor:
+        out = torch.zeros(self.rows, self.F, dtype=dtype,
+                          device=self.payload.device)
+        return mixed_dequantize(self.payload, self.params, self.plan, out)
+
+    def record_stream(self, stream) -> None:
+        for t in (self.payload, self.params, self._desc):
+            if t is not None and t.is_cuda:
+                t.record_stream(stream)
+
+
+def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
          src_scale: Optional[Tensor], dst_scale: Optional[Tensor],
          out: Optional[Tensor] = None, addend: Optional[Tensor] = None,
          wave_index: Optional[bool] = None,
@@ -295,8 +378,22 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
     tensors), same result bit for bit. Ignored on the CPU.
     ``packed_depth``: row fetches in flight per lane in that kernel
     (None = PACKED_DEPTH).
+    ``x_remote`` may be a :class:`QuantRemote`. For GPU fp32
+    (``QuantRemote.fusable``) the quantized-gather kernel runs and a
+    ``packed`` operand is ignored for that call: the two gathers are not
+    combined, and the quantized one wins. Otherwise (CPU, bf16) the block
+    is dequantized first and the call proceeds as with a tensor.
     """
     indptr, indices, num_rows = view.indptr, view.indices, view.nrows
+    quant = None
+    if isinstance(x_remote, QuantRemote):
+        if x_remote.fusable(x_local):
+            assert x_remote.F == x_local.shape[1]
+            assert view.max_col < x_local.shape[0] + x_remote.rows, \
+                'the view names a column past the remote rows described'
+            quant, x_remote, packed = x_remote, None, None
+        else:
+            x_remote = x_remote.dequantize(x_local.dtype)
     if not x_local.is_cuda and view.col_blocked:
         raise RuntimeError('column-blocked SpmmView is GPU-only (the CPU '
                            'fallback consumes indptr, which the blocked '
@@ -326,7 +423,9 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote: Optional[Tensor],
                                else wave_index),
                           packed.buf if packed is not None else empty,
                           int(PACKED_DEPTH if packed_depth is None
-                              else packed_depth))
+                              else packed_depth),
+                          quant.payload if quant is not None else empty,
+                          quant.descriptors() if quant is not None else empty)
         return out
     x = (torch.cat([x_local, x_remote], dim=0)
          if x_remote is not None and x_remote.numel() else x_local)

@@ -49,6 +49,10 @@ class GraphEngine:
         self.base_seed = base_seed
         self.compute_dtype = torch.float32   # set to torch.bfloat16 for bf16 mode
         self._rng_counter = 0
+        # quantized exchanges hand the SpMM the wire buffer instead of a
+        # dequantized block (GPU fp32; ops/dist_agg.py). None: on iff env
+        # ADAQP_FUSED_DEQUANT=1, read at each propagation; a bool wins.
+        self.fused_dequant: Optional[bool] = None
         self.timer = Timer(enabled=False, cuda=self.device.type == 'cuda',
                            mode='events')
         self.is_tracing = False

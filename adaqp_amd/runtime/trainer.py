@@ -59,6 +59,8 @@ class Trainer:
             self.cfg['model']['fused_norm'] = True
         if getattr(args, 'fused_loss', False):
             rt['fused_loss'] = True
+        if getattr(args, 'fused_dequant', False):
+            rt['fused_dequant'] = True
         self.mode = RunMode(args.mode)
         self.model_type = MODEL_MAP[args.model_name]
         self.comm = Communicator(backend=getattr(args, 'backend', None),
@@ -138,6 +140,7 @@ class Trainer:
         self.engine = GraphEngine(self.graph, self.mode, self.model_type,
                                   msg_dims, agg_type=m['aggregator_type'],
                                   device=self.comm.device)
+        self.engine.fused_dequant = self.cfg['runtime'].get('fused_dequant')
         if getattr(self.args, 'time_breakdown', False):
             self.engine.timer.enabled = True
         if getattr(self.args, 'dtype', 'fp32') == 'bf16':

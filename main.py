@@ -58,6 +58,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help='one-op masked training loss (sets runtime.fused_loss; '
                         'ADAQP_FUSED_LOSS=1 is the env switch when neither '
                         'sets it)')
+    p.add_argument('--fused_dequant', action='store_true',
+                   help='SpMM gathers remote columns from the quantized wire '
+                        'buffer, GPU fp32 (sets runtime.fused_dequant; '
+                        'ADAQP_FUSED_DEQUANT=1 is the env switch when neither '
+                        'sets it)')
     return p
 
 
