@@ -602,6 +602,19 @@ void launch_spmm_packed(
     const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
     const int32_t* seg_e1, const int32_t* seg_part, float* part,
     const float* addend, int64_t n_seg, int64_t F, int64_t n_local);
+// spmm_packed_bf16.hip
+bool spmm_packable_bf16(int64_t F);
+int64_t packed_bf16_meta_bytes(int64_t F);
+int64_t packed_bf16_row_stride(int64_t F);
+int64_t packed_bf16_buffer_bytes(int64_t n, int64_t F);
+torch::Tensor pack_rows_bf16(torch::Tensor x);
+void launch_spmm_packed_bf16(
+    dim3 grid, dim3 block, hipStream_t s, int depth,
+    const int32_t* indices, const ushort* xl, const ushort* xr,
+    const uint8_t* pk, ushort* y, const float* src_scale,
+    const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
+    const int32_t* seg_e1, const int32_t* seg_part, float* part,
+    const ushort* addend, int64_t n_seg, int64_t F, int64_t n_local);
 // spmm_quant.hip
 int64_t quant_pad_bytes();
 torch::Tensor quant_row_desc(torch::Tensor tab, torch::Tensor params);
@@ -776,8 +789,29 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
         combine();
         return;
     }
-    // packed operand (pack_rows(xl); a 0-element tensor means "none"):
-    // local columns are gathered from it, the result is the same bits
+    // packed operand (pack_rows(xl), or pack_rows_bf16(xl) for bf16; a
+    // 0-element tensor means "none"): local columns are gathered from it,
+    // the result is the same bits
+    if (packed.numel() && bf16) {
+        CHECK_DEV(packed); CHECK_CONTIG(packed);
+        TORCH_CHECK(spmm_packable_bf16(F) && n_local > 0 &&
+                    n_local < (1ll << 31),
+                    "packed bf16 spmm expects F % 8 == 0, 8 <= F <= 256 and "
+                    "between 1 and 2^31 - 1 local rows");
+        TORCH_CHECK(packed.scalar_type() == torch::kUInt8 &&
+                    packed.numel() == packed_bf16_buffer_bytes(n_local, F),
+                    "packed operand does not match xl (pack_rows_bf16(xl))");
+        launch_spmm_packed_bf16(
+            grid, block, s, (int)packed_depth, ind_p,
+            reinterpret_cast<const ushort*>(xl.data_ptr()),
+            reinterpret_cast<const ushort*>(xr_ptr),
+            packed.data_ptr<uint8_t>(),
+            reinterpret_cast<ushort*>(y.data_ptr()), ss_p, ds_p,
+            sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(),
+            reinterpret_cast<const ushort*>(ad_ptr), n_seg, F, n_local);
+        combine();
+        return;
+    }
     if (packed.numel()) {
         CHECK_DEV(packed); CHECK_CONTIG(packed);
         TORCH_CHECK(!bf16 && spmm_packable(F) && n_local > 0,
@@ -930,6 +964,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("packed_meta_bytes", &packed_meta_bytes);
     m.def("packed_row_stride", &packed_row_stride);
     m.def("packed_buffer_bytes", &packed_buffer_bytes);
+    m.def("pack_rows_bf16", &pack_rows_bf16,
+          "fixed-stride packed copy of a sparse bf16 [N,F] tensor for the "
+          "bf16 packed-gather SpMM (CDNA4)");
+    m.def("spmm_packable_bf16", &spmm_packable_bf16);
+    m.def("packed_bf16_meta_bytes", &packed_bf16_meta_bytes);
+    m.def("packed_bf16_row_stride", &packed_bf16_row_stride);
+    m.def("packed_bf16_buffer_bytes", &packed_bf16_buffer_bytes);
     m.def("colsum", &colsum,
           "deterministic column sum of a [N,F] fp32/bf16 matrix, fp32 "
           "accumulate (CDNA4)");

@@ -28,6 +28,14 @@ _ones_cache: dict = {}
 # defaults of the two switches (docs/TUNING.md); the environment overrides
 SPMM_PACKED_DEFAULT = '1'
 AGG0_CACHE_DEFAULT = '1'
+# ADAQP_SPMM_PACKED_BF16=1: a bf16 engine packs too (csrc/spmm_packed_bf16.hip).
+# It has an effect only where ADAQP_SPMM_PACKED is on.
+SPMM_PACKED_BF16_DEFAULT = '0'
+
+
+def spmm_packed_bf16_on() -> bool:
+    return os.environ.get('ADAQP_SPMM_PACKED_BF16',
+                          SPMM_PACKED_BF16_DEFAULT) == '1'
 
 
 def _ones_row(n: int, device, dtype) -> Tensor:
@@ -222,14 +230,16 @@ class _SageMeanFn(torch.autograd.Function):
     ReLU + dropout); the cast input is then packed once and the forward
     SpMMs gather from the packed copy (same bits, fewer bytes per edge).
     A tensor that does not qualify (``ops.kernels.packable``) is not
-    packed. The backward SpMM gathers a dense GEMM output and never is."""
+    packed, except that with ADAQP_SPMM_PACKED_BF16=1 a bf16 one goes
+    through ``pack_rows_bf16``. The backward SpMM gathers a dense GEMM
+    output and never is."""
 
     @staticmethod
     def forward(ctx, x: Tensor, w1: Tensor, w2: Tensor, b1: Tensor,
                 b2: Tensor, engine, layer: int, is_train: bool,
                 pack: bool = False) -> Tensor:
         from ..ops.dist_agg import propagate
-        from ..ops.kernels import pack_rows
+        from ..ops.kernels import pack_rows, pack_rows_bf16
         from ..helpers import PropagationMode
         num_inner = engine.graph.num_inner
         key = _agg_cache_key(ctx, engine, x, layer, is_train)
@@ -237,6 +247,9 @@ class _SageMeanFn(torch.autograd.Function):
         if h is None:
             xa = x.to(engine.compute_dtype).contiguous()
             packed = pack_rows(xa) if pack else None
+            if (pack and packed is None and xa.dtype == torch.bfloat16
+                    and spmm_packed_bf16_on()):
+                packed = pack_rows_bf16(xa)
             kw = {} if packed is None else {'packed': packed}
             h = propagate(engine, xa, layer, is_train,
                           PropagationMode.Forward, **kw)

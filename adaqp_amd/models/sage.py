@@ -99,12 +99,20 @@ class DistSAGE(nn.Module):
         non-zero in expectation (about a quarter with the ReLU), for the
         nn.Dropout stack and the fused-norm stack alike. The tensor must
         qualify once cast to the compute dtype (fp32, F % 4 == 0,
-        F <= 256). ADAQP_SPMM_PACKED=0/1 switches the whole thing."""
+        F <= 256). ADAQP_SPMM_PACKED=0/1 switches the whole thing. With
+        ADAQP_SPMM_PACKED_BF16=1 (off by default) a bf16 engine qualifies
+        too (F % 8 == 0, F <= 256); h may still be fp32 there, the layer
+        casts it."""
         if os.environ.get('ADAQP_SPMM_PACKED',
                           _common.SPMM_PACKED_DEFAULT) != '1':
             return False
-        return (i > 0 and self.training and self.dropout.p >= 0.5
-                and engine.compute_dtype == torch.float32
+        if not (i > 0 and self.training and self.dropout.p >= 0.5):
+            return False
+        if (engine.compute_dtype == torch.bfloat16
+                and _common.spmm_packed_bf16_on()):
+            return (h.is_cuda and h.dim() == 2 and h.shape[0] > 0
+                    and 8 <= h.shape[1] <= 256 and h.shape[1] % 8 == 0)
+        return (engine.compute_dtype == torch.float32
                 and h.dtype == torch.float32 and packable(h))
 
     def forward(self, engine, feats: Tensor) -> Tensor:

@@ -10,7 +10,7 @@ same hash RNG) used by unit tests and the CPU/gloo plumbing config.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -275,6 +275,43 @@ def pack_rows(x: Tensor) -> Optional[PackedRows]:
     return PackedRows(native().pack_rows(x), x.shape[0], x.shape[1])
 
 
+def packable_bf16(x: Tensor) -> bool:
+    """True if ``x`` can be the packed operand of a bf16 :func:`spmm`: a GPU
+    bf16 contiguous [N, F] tensor with at least one row, F % 8 == 0 and
+    8 <= F <= 256."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2
+            and x.is_contiguous() and x.shape[0] > 0
+            and 8 <= x.shape[1] <= PACK_MAX_FEATS and x.shape[1] % 8 == 0)
+
+
+class PackedRowsBf16:
+    """Packed copy of a sparse [N, F] bf16 tensor (csrc/spmm_packed_bf16.hip
+    has the layout): per row ``F/8`` 16-bit words (8-bit presence mask,
+    8-bit count of kept values before the group; 0xFFFF in every word of an
+    overflow row) padded to ``meta_bytes``, then up to ``F/2`` kept bf16 bit
+    patterns; rows are ``stride`` bytes apart in the uint8 buffer ``buf``.
+    Rows with more than F/2 non-zero bit patterns are overflow rows and are
+    read from the dense tensor."""
+
+    def __init__(self, buf: Tensor, rows: int, feats: int):
+        C = native()
+        self.buf, self.rows, self.feats = buf, rows, feats
+        self.meta_bytes = int(C.packed_bf16_meta_bytes(feats))
+        self.stride = int(C.packed_bf16_row_stride(feats))
+
+    def matches(self, x: Tensor) -> bool:
+        return (packable_bf16(x) and x.shape[0] == self.rows
+                and x.shape[1] == self.feats and x.device == self.buf.device)
+
+
+def pack_rows_bf16(x: Tensor) -> Optional[PackedRowsBf16]:
+    """:func:`pack_rows` for bf16: one pass of the native bf16 pack kernel;
+    ``None`` when ``x`` does not qualify (see :func:`packable_bf16`)."""
+    if not packable_bf16(x):
+        return None
+    return PackedRowsBf16(native().pack_rows_bf16(x), x.shape[0], x.shape[1])
+
+
 def resolve_fused_dequant(flag: Optional[bool]) -> bool:
     """``None`` -> on iff env ``ADAQP_FUSED_DEQUANT=1``; an explicit bool
     wins. (``GraphEngine.fused_dequant`` is the flag; ops/dist_agg.py
@@ -359,7 +396,7 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
          src_scale: Optional[Tensor], dst_scale: Optional[Tensor],
          out: Optional[Tensor] = None, addend: Optional[Tensor] = None,
          wave_index: Optional[bool] = None,
-         packed: Optional[PackedRows] = None,
+         packed: Union[PackedRows, 'PackedRowsBf16', None] = None,
          packed_depth: Optional[int] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
@@ -373,7 +410,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     result is ``spmm(...) + addend`` bit for bit, added in the kernel's
     epilogue instead of a separate pass.
     ``wave_index``: which SW == 64 kernel runs (None = WAVE_INDEX).
-    ``packed``: ``pack_rows(x_local)``; local columns are then gathered
+    ``packed``: ``pack_rows(x_local)`` for fp32 or
+    ``pack_rows_bf16(x_local)`` for bf16; local columns are then gathered
     from the packed copy (remote columns and overflow rows from the dense
     tensors), same result bit for bit. Ignored on the CPU.
     ``packed_depth``: row fetches in flight per lane in that kernel
@@ -382,7 +420,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     (``QuantRemote.fusable``) the quantized-gather kernel runs and a
     ``packed`` operand is ignored for that call: the two gathers are not
     combined, and the quantized one wins. Otherwise (CPU, bf16) the block
-    is dequantized first and the call proceeds as with a tensor.
+    is dequantized first and the call proceeds as with a tensor: under
+    bf16 it is the dense remote operand of a packed call.
     """
     indptr, indices, num_rows = view.indptr, view.indices, view.nrows
     quant = None

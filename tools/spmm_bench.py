@@ -10,7 +10,8 @@ as median (min..max) of per-call device-event times, after checking that
 they produce the same bits.
 
 ``--packed 0,1`` does the same for the packed-gather kernel against the
-dense one (fp32, F % 4 == 0, F <= 256), once per ``--density``: the input
+dense one (fp32 with F % 4 == 0 or ``--dtype bf16`` with F % 8 == 0,
+F <= 256), once per ``--density``: the input
 is synthetic, zeros placed i.i.d. per element, and the pack kernel is timed
 on its own. ``--packed-depth 4,8`` adds one packed variant per number of
 row fetches in flight."""
@@ -138,8 +139,9 @@ def _fmt(t):
 
 
 def packed_bench(args, view, x, src, dst, E, head):
-    from adaqp_amd.ops.kernels import pack_rows, spmm
-    assert x.dtype == torch.float32, '--packed is fp32 only'
+    from adaqp_amd.ops.kernels import pack_rows, pack_rows_bf16, spmm
+    if x.dtype == torch.bfloat16:
+        pack_rows = pack_rows_bf16
     want = [int(m) for m in args.packed.split(',')]
     depths = [int(d) for d in args.packed_depth.split(',')]
     # variants: None = dense kernel, d = packed kernel with d fetches in flight
@@ -170,7 +172,7 @@ def packed_bench(args, view, x, src, dst, E, head):
               f'{["dense" if v is None else f"packed/{v}" for v in variants]}'
               f' bit-identical: {same}')
         print(f'  pack kernel: {_fmt(tp)}, '
-              f'{(xd.numel() * 4 + pk.buf.numel()) / (statistics.median(tp) * 1e-3) / 1e12:.2f}'
+              f'{(xd.numel() * xd.element_size() + pk.buf.numel()) / (statistics.median(tp) * 1e-3) / 1e12:.2f}'
               f' TB/s read + written (upper bound on bytes)')
         times = {v: [] for v in variants}
         for _ in range(args.iters):
