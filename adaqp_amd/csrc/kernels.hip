@@ -625,6 +625,15 @@ void launch_spmm_quant(
     const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
     const int32_t* seg_e1, const int32_t* seg_part, float* part,
     const float* addend, int64_t n_seg, int64_t F, int64_t n_local);
+// spmm_mixed.hip
+torch::Tensor round_rows_bf16(torch::Tensor x, int64_t seed, int64_t tag_base);
+void spmm_bf16in_shape(int64_t F, int* ve, int* sw);
+void launch_spmm_bf16in(
+    hipStream_t s, const int32_t* indices, const ushort* xl, const ushort* xr,
+    float* y, const float* src_scale, const float* dst_scale,
+    const int32_t* seg_row, const int32_t* seg_e0, const int32_t* seg_e1,
+    const int32_t* seg_part, float* part, const float* addend,
+    int64_t n_seg, int64_t F, int64_t n_local);
 
 static inline hipStream_t cur_stream() {
     return at::cuda::getCurrentHIPStream().stream();
@@ -881,6 +890,103 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
     combine();
 }
 
+// Mixed-precision spmm_csr (spmm_mixed.hip): xl / xr are bf16 and are only
+// gathered; y, addend and the partial slots are fp32. Same bits as spmm_csr
+// on the widened operands.
+void spmm_csr_bf16in(torch::Tensor indices, torch::Tensor xl,
+                     torch::Tensor xr, torch::Tensor y,
+                     torch::Tensor src_scale, torch::Tensor dst_scale,
+                     torch::Tensor seg_row, torch::Tensor seg_e0,
+                     torch::Tensor seg_e1, torch::Tensor seg_part,
+                     torch::Tensor zero_rows, torch::Tensor part_ptr,
+                     int64_t n_part, torch::Tensor addend) {
+    CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
+    TORCH_CHECK(xl.dim() == 2 && xl.scalar_type() == torch::kBFloat16 &&
+                y.dim() == 2 && y.scalar_type() == torch::kFloat32,
+                "mixed spmm expects bf16 [N, F] rows and an fp32 [nrows, F] y");
+    const int64_t F = xl.size(1);
+    const int64_t n_local = xl.size(0);
+    const int64_t n_seg = seg_row.numel();
+    TORCH_CHECK(F > 0 && F % 2 == 0 && y.size(1) == F,
+                "mixed spmm needs an even feature dim, the same in x and y");
+    int ve, sw;
+    spmm_bf16in_shape(F, &ve, &sw);
+    // a lane's ve bf16 values are one 2 * ve-byte load, its results one or
+    // two 16-byte (ve = 2: one 8-byte) fp32 accesses
+    const uintptr_t in_al = 2 * ve, out_al = ve == 2 ? 8 : 16;
+    auto aligned = [](const void* p, uintptr_t a) {
+        return reinterpret_cast<uintptr_t>(p) % a == 0;
+    };
+    const ushort* xr_ptr = nullptr;
+    int64_t n_remote = 0;
+    if (xr.numel()) {
+        CHECK_DEV(xr); CHECK_CONTIG(xr);
+        TORCH_CHECK(xr.dim() == 2 && xr.size(1) == F &&
+                    xr.scalar_type() == torch::kBFloat16,
+                    "mixed spmm: the remote block must be bf16 [R, F]");
+        xr_ptr = reinterpret_cast<const ushort*>(xr.data_ptr());
+        n_remote = xr.size(0);
+    }
+    const float* ad_ptr = nullptr;
+    if (addend.dim() == 2) {        // a 1-D empty tensor means "none"
+        CHECK_DEV(addend); CHECK_CONTIG(addend);
+        TORCH_CHECK(addend.size(0) == y.size(0) && addend.size(1) == F &&
+                    addend.scalar_type() == torch::kFloat32,
+                    "mixed spmm: addend must be fp32 [nrows, F]");
+        ad_ptr = addend.numel() ? addend.data_ptr<float>() : nullptr;
+    }
+    TORCH_CHECK(aligned(xl.data_ptr(), in_al) && aligned(xr_ptr, in_al) &&
+                aligned(y.data_ptr(), out_al) && aligned(ad_ptr, out_al),
+                "mixed spmm: operands must be aligned to the vector widths");
+    for (const torch::Tensor* t : {&indices, &seg_row, &seg_e0, &seg_e1,
+                                   &seg_part, &zero_rows, &part_ptr})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous(),
+                    "mixed spmm: the view's arrays must be on the GPU");
+    TORCH_CHECK((!src_scale.numel() || src_scale.is_cuda()) &&
+                (!dst_scale.numel() || dst_scale.is_cuda()),
+                "mixed spmm: scale vectors must be on the GPU");
+    TORCH_CHECK(indices.scalar_type() == torch::kInt32 &&
+                seg_row.scalar_type() == torch::kInt32 &&
+                seg_e0.scalar_type() == torch::kInt32 &&
+                seg_e1.scalar_type() == torch::kInt32 &&
+                seg_part.scalar_type() == torch::kInt32 &&
+                seg_e0.numel() == n_seg && seg_e1.numel() == n_seg &&
+                seg_part.numel() == n_seg &&
+                zero_rows.scalar_type() == torch::kInt32 &&
+                part_ptr.scalar_type() == torch::kInt32 &&
+                part_ptr.numel() == zero_rows.numel() + 1,
+                "mixed spmm expects the int32 arrays SpmmView builds");
+    TORCH_CHECK(n_part >= 0 && n_part <= n_seg, "bad partial slot count");
+    TORCH_CHECK(!src_scale.numel() ||
+                (src_scale.scalar_type() == torch::kFloat32 &&
+                 src_scale.numel() >= n_local + n_remote),
+                "mixed spmm: src_scale must be fp32 and cover every column");
+    TORCH_CHECK(!dst_scale.numel() ||
+                (dst_scale.scalar_type() == torch::kFloat32 &&
+                 dst_scale.numel() == y.size(0)),
+                "mixed spmm: dst_scale must be fp32 [nrows]");
+    auto s = cur_stream();
+    torch::Tensor part = torch::empty(
+        {n_part, F}, y.options().dtype(torch::kFloat32));
+    if (n_seg)
+        launch_spmm_bf16in(
+            s, indices.data_ptr<int32_t>(),
+            reinterpret_cast<const ushort*>(xl.data_ptr()), xr_ptr,
+            y.data_ptr<float>(),
+            src_scale.numel() ? src_scale.data_ptr<float>() : nullptr,
+            dst_scale.numel() ? dst_scale.data_ptr<float>() : nullptr,
+            seg_row.data_ptr<int32_t>(), seg_e0.data_ptr<int32_t>(),
+            seg_e1.data_ptr<int32_t>(), seg_part.data_ptr<int32_t>(),
+            part.data_ptr<float>(), ad_ptr, n_seg, F, n_local);
+    if (zero_rows.numel()) {
+        const dim3 zb(256), zg((zero_rows.numel() + 3) / 4);
+        combine_parts_kernel<float><<<zg, zb, 0, s>>>(
+            y.data_ptr<float>(), part.data_ptr<float>(),
+            zero_rows.data_ptr<int32_t>(), part_ptr.data_ptr<int32_t>(),
+            ad_ptr, zero_rows.numel(), F);
+    }
+}
+
 
 // norm_act.hip
 void norm_act_fwd(torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
@@ -953,6 +1059,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("packed_depth") = 4,
           pybind11::arg("q_payload") = torch::Tensor(),
           pybind11::arg("q_desc") = torch::Tensor());
+    m.def("spmm_csr_bf16in", &spmm_csr_bf16in,
+          "spmm_csr gathering bf16 rows into fp32 accumulators, addend and "
+          "output (CDNA4)",
+          pybind11::arg("indices"), pybind11::arg("xl"), pybind11::arg("xr"),
+          pybind11::arg("y"), pybind11::arg("src_scale"),
+          pybind11::arg("dst_scale"), pybind11::arg("seg_row"),
+          pybind11::arg("seg_e0"), pybind11::arg("seg_e1"),
+          pybind11::arg("seg_part"), pybind11::arg("zero_rows"),
+          pybind11::arg("part_ptr"), pybind11::arg("n_part"),
+          pybind11::arg("addend"));
+    m.def("round_rows_bf16", &round_rows_bf16,
+          "fp32 [N, F] -> bf16 [N, F] with unbiased stochastic rounding from "
+          "the counter hash (CDNA4)",
+          pybind11::arg("x"), pybind11::arg("seed"),
+          pybind11::arg("tag_base") = 0);
     m.def("quant_row_desc", &quant_row_desc,
           "per-remote-row {offset, bits, inv, rmin} descriptors of one "
           "quantized exchange, for the quantized-gather SpMM (CDNA4)");

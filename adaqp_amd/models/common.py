@@ -232,7 +232,8 @@ class _SageMeanFn(torch.autograd.Function):
     A tensor that does not qualify (``ops.kernels.packable``) is not
     packed, except that with ADAQP_SPMM_PACKED_BF16=1 a bf16 one goes
     through ``pack_rows_bf16``. The backward SpMM gathers a dense GEMM
-    output and never is."""
+    output and never is; with ADAQP_BWD_GATHER_BF16=1 an fp32 engine
+    gathers it rounded to bf16 instead (ops/dist_agg.py)."""
 
     @staticmethod
     def forward(ctx, x: Tensor, w1: Tensor, w2: Tensor, b1: Tensor,
@@ -262,7 +263,7 @@ class _SageMeanFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g: Tensor):
-        from ..ops.dist_agg import propagate
+        from ..ops.dist_agg import propagate, next_bwd_gather_seed
         from ..helpers import PropagationMode
         xs, h, w1, w2 = ctx.saved_tensors
         engine = ctx.engine
@@ -272,12 +273,17 @@ class _SageMeanFn(torch.autograd.Function):
             assert ctx.in_rows == engine.graph.num_inner
             gh = (g @ w2.t()).to(engine.compute_dtype).contiguous()
             gx_self = g @ w1.t()
+            # ADAQP_BWD_GATHER_BF16=1 (fp32 engines): the SpMM gathers gh
+            # rounded to bf16; addend and result stay fp32
+            seed = next_bwd_gather_seed(engine, gh, ctx.layer)
+            kw = {} if seed is None else {'gather_bf16': seed}
             if gx_self.dtype == gh.dtype == ctx.in_dtype:
                 gx = propagate(engine, gh, ctx.layer, True,
-                               PropagationMode.Backward, addend=gx_self)
+                               PropagationMode.Backward, addend=gx_self, **kw)
             else:
                 gx = propagate(engine, gh, ctx.layer, True,
-                               PropagationMode.Backward).to(ctx.in_dtype)
+                               PropagationMode.Backward,
+                               **kw).to(ctx.in_dtype)
                 gx.add_(gx_self)        # promotes gx_self: exact widening
         gw1 = xs.t() @ g if ctx.needs_input_grad[1] else None
         gw2 = h.t() @ g if ctx.needs_input_grad[2] else None

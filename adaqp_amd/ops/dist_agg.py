@@ -27,7 +27,8 @@ from torch import Tensor
 from ..helpers import BitType, DistGNNType, PropagationMode
 from ..comm.communicator import Communicator
 from .kernels import (mixed_quantize, mixed_dequantize, spmm, QuantRemote,
-                      resolve_fused_dequant)
+                      resolve_fused_dequant, resolve_bwd_gather_bf16,
+                      round_rows_bf16)
 
 
 # --------------------------------------------------------------------------
@@ -64,11 +65,13 @@ def _fused_dequant(engine, x_local: Tensor, key: str, quant: bool) -> bool:
             and engine.plans[key].recv.row_tab is not None)
 
 
-def _exchange_finish(engine, staged, key: str, fused: bool = False):
+def _exchange_finish(engine, staged, key: str, fused: bool = False,
+                     remote_dtype: Optional[torch.dtype] = None):
     """Transport + consumer-side kernels (dequant/scatter). ``fused``
     (quantized exchanges only): return a :class:`QuantRemote` over the
     received wire buffer; the only consumer-side kernel is then the one
-    that writes its row descriptors."""
+    that writes its row descriptors. ``remote_dtype`` (quantized, not
+    fused): dtype of the dequantized block instead of the sender's."""
     comm = Communicator.ctx
     g = engine.graph
     kind, a, b, dtype = staged
@@ -98,7 +101,7 @@ def _exchange_finish(engine, staged, key: str, fused: bool = False):
             if remote.rows:
                 remote.descriptors()
         return remote
-    out = torch.empty(g.num_remote, plan.F, dtype=dtype,
+    out = torch.empty(g.num_remote, plan.F, dtype=remote_dtype or dtype,
                       device=payload.device)
     with engine.timer.record(f'{key}_dequant'):
         mixed_dequantize(recv_payload, recv_params, plan.recv, out)
@@ -141,15 +144,20 @@ def _scales(engine, mode: PropagationMode) -> Tuple[Optional[Tensor], Optional[T
 
 
 def _agg(engine, view, x_local: Tensor, x_remote, src_scale, dst_scale,
-         out=None, addend=None, packed=None) -> Tensor:
+         out=None, addend=None, packed=None, out_dtype=None) -> Tensor:
     """SpMM over one SpmmView. src_scale is the full [N] vector; dst_scale
     and the optional [num_inner, F] addend are sliced to the view's row
     range. ``packed``: ``pack_rows(x_local)`` (the gather's source rows, so
-    the same handle serves every view)."""
+    the same handle serves every view). ``out_dtype``: the mixed call, bf16
+    rows gathered into an fp32 result."""
     ds = (dst_scale[view.base:view.base + view.nrows]
           if dst_scale is not None else None)
     ad = (addend[view.base:view.base + view.nrows]
           if addend is not None else None)
+    if out_dtype is not None:
+        assert packed is None
+        return spmm(view, x_local, x_remote, src_scale, ds, out=out,
+                    addend=ad, out_dtype=out_dtype)
     if packed is not None:
         return spmm(view, x_local, x_remote, src_scale, ds, out=out,
                     addend=ad, packed=packed)
@@ -166,6 +174,56 @@ def _addend_kw(addend, packed=None) -> dict:
     return kw
 
 
+# --------------------------------------------------------------------------
+# bf16 gather operand of the fp32 backward aggregation (opt-in)
+#
+# The backward SpMM of an fp32 engine gathers a dense GEMM output at 4F bytes
+# per edge. With the switch on it gathers rows rounded to bf16 WITHOUT BIAS
+# (round_rows_bf16: stochastic rounding, as the quantizer does for remote
+# rows at 2/4/8 bits) and keeps accumulators, addend and result in fp32
+# (csrc/spmm_mixed.hip). Only the SpMM operands change: the exchange reads
+# the dense fp32 tensor, so wire format, plans, assigner and tracing are as
+# without it, and the rounding seeds come from a counter of their own, so the
+# quantization stream (engine.next_seed) is too.
+# --------------------------------------------------------------------------
+
+_GATHER_SALT = 0x62663136      # keeps the stream apart from the fused norm's
+
+
+def bwd_gather_seed(engine, layer: int, counter: int) -> int:
+    """Rounding seed of the ``counter``-th bf16-gather backward of
+    ``engine``: the hash chain of models/norm.py over (base_seed, layer,
+    counter, rank)."""
+    from ..models.norm import derive_seed
+    rank = Communicator.ctx.rank if Communicator.ctx is not None else 0
+    return derive_seed(engine.base_seed ^ _GATHER_SALT, layer, counter, rank)
+
+
+def next_bwd_gather_seed(engine, x: Tensor, layer: int) -> Optional[int]:
+    """What a backward caller passes to ``propagate(gather_bf16=...)`` for
+    the operand ``x``: ``None`` unless the switch is on, the engine computes
+    in fp32 and ``x`` is an fp32 [N, F] tensor with even F; else the next
+    seed (``engine.bwd_gather_calls`` counts them)."""
+    if not (resolve_bwd_gather_bf16(getattr(engine, 'bwd_gather_bf16', None))
+            and engine.compute_dtype == torch.float32
+            and x.dtype == torch.float32 and x.dim() == 2
+            and x.shape[1] > 0 and x.shape[1] % 2 == 0):
+        return None
+    seed = bwd_gather_seed(engine, layer, engine.bwd_gather_calls)
+    engine.bwd_gather_calls += 1
+    return seed
+
+
+def _round_remote(remote, seed: int, num_local: int):
+    """The remote operand of a bf16-gather SpMM: a full-precision block is
+    rounded with the tags that follow the local rows'; a block dequantized
+    into bf16, or a QuantRemote (which spmm dequantizes into one), is
+    already that."""
+    if isinstance(remote, Tensor) and remote.dtype == torch.float32:
+        return round_rows_bf16(remote, seed, tag_base=num_local)
+    return remote
+
+
 def _self_term(engine, x_local: Tensor, mode: PropagationMode) -> Tensor:
     """SAGE 'gcn' aggregator self term (reference ops.py:44-47,57-64)."""
     I = engine.graph.num_inner
@@ -180,18 +238,30 @@ def _self_term(engine, x_local: Tensor, mode: PropagationMode) -> Tensor:
 
 def full_propagation(engine, x_local: Tensor, key: str, is_train: bool,
                      mode: PropagationMode, addend=None,
-                     packed=None) -> Tensor:
+                     packed=None, gather_bf16: Optional[int] = None) -> Tensor:
     quant = engine.bit_type == BitType.QUANT and is_train
     if _fused_dequant(engine, x_local, key, quant):
         remote = _exchange_finish(
             engine, _exchange_start(engine, x_local, key, True), key,
             fused=True)
+    elif quant and gather_bf16 is not None:
+        # dequantized straight into the bf16 block the SpMM gathers
+        remote = _exchange_finish(
+            engine, _exchange_start(engine, x_local, key, True), key,
+            remote_dtype=torch.bfloat16)
     else:
         remote = _exchange(engine, x_local, key, is_train)
     src_scale, dst_scale, add_self = _scales(engine, mode)
     with engine.timer.record(f'{key}_full_aggregation'):
-        y = _agg(engine, engine.full_view, x_local, remote, src_scale, dst_scale,
-                 **_addend_kw(addend, packed))
+        if gather_bf16 is not None:
+            y = _agg(engine, engine.full_view,
+                     round_rows_bf16(x_local, gather_bf16),
+                     _round_remote(remote, gather_bf16, x_local.shape[0]),
+                     src_scale, dst_scale, addend=addend,
+                     out_dtype=torch.float32)
+        else:
+            y = _agg(engine, engine.full_view, x_local, remote, src_scale,
+                     dst_scale, **_addend_kw(addend, packed))
         if add_self:
             y = y + _self_term(engine, x_local, mode)
     return y
@@ -199,7 +269,8 @@ def full_propagation(engine, x_local: Tensor, key: str, is_train: bool,
 
 def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
                            mode: PropagationMode, addend=None,
-                           packed=None) -> Tensor:
+                           packed=None,
+                           gather_bf16: Optional[int] = None) -> Tensor:
     """Central aggregation (default stream) overlapped with
     quant->all_to_all->dequant (comm stream).
 
@@ -216,6 +287,13 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
     g = engine.graph
     on_gpu = x_local.is_cuda
     quant = engine.bit_type == BitType.QUANT and is_train
+    # bf16 gather: both views read ONE rounded copy of the local rows (xg);
+    # the exchange and the self term keep reading the fp32 x_local
+    bf16 = gather_bf16 is not None
+    agg_kw = ({'addend': addend, 'out_dtype': torch.float32} if bf16
+              else _addend_kw(addend, packed))
+    deq_kw = {'remote_dtype': torch.bfloat16} if bf16 and quant else {}
+    xg = x_local
 
     if on_gpu:
         cur = torch.cuda.current_stream()
@@ -232,29 +310,41 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
         # central rows only touch local columns -> enqueue NOW, before
         # the transport can block the host
         with engine.timer.record(f'{key}_central_aggregation'):
-            _agg(engine, engine.central_view, x_local, None, src_scale,
-                 dst_scale, out=y[:C], **_addend_kw(addend, packed))
+            if bf16:
+                xg = round_rows_bf16(x_local, gather_bf16)
+            _agg(engine, engine.central_view, xg, None, src_scale,
+                 dst_scale, out=y[:C], **agg_kw)
         # fused dequant: `remote` is a QuantRemote (the wire buffer and its
         # row descriptors); the marginal SpMM gathers from it, and a packed
         # operand is ignored for that view (ops/kernels.py::spmm)
         fused_kw = ({'fused': True}
-                    if _fused_dequant(engine, x_local, key, quant) else {})
+                    if _fused_dequant(engine, x_local, key, quant) else deq_kw)
         with torch.cuda.stream(engine.comm_stream):
             remote = _exchange_finish(engine, staged, key, **fused_kw)
             engine.remote_ready.record(engine.comm_stream)
         torch.cuda.current_stream().wait_event(engine.remote_ready)
         remote.record_stream(torch.cuda.current_stream())
         with engine.timer.record(f'{key}_marginal_aggregation'):
-            _agg(engine, engine.marginal_view, x_local, remote, src_scale,
-                 dst_scale, out=y[C:], **_addend_kw(addend, packed))
+            if bf16:
+                remote = _round_remote(remote, gather_bf16, x_local.shape[0])
+            _agg(engine, engine.marginal_view, xg, remote, src_scale,
+                 dst_scale, out=y[C:], **agg_kw)
     else:
-        remote = _exchange(engine, x_local, key, is_train)
+        if deq_kw:
+            remote = _exchange_finish(
+                engine, _exchange_start(engine, x_local, key, True), key,
+                **deq_kw)
+        else:
+            remote = _exchange(engine, x_local, key, is_train)
+        if bf16:
+            xg = round_rows_bf16(x_local, gather_bf16)
+            remote = _round_remote(remote, gather_bf16, x_local.shape[0])
         with engine.timer.record(f'{key}_central_aggregation'):
-            y_c = _agg(engine, engine.central_view, x_local, None, src_scale,
-                       dst_scale, **_addend_kw(addend, packed))
+            y_c = _agg(engine, engine.central_view, xg, None, src_scale,
+                       dst_scale, **agg_kw)
         with engine.timer.record(f'{key}_marginal_aggregation'):
-            y_m = _agg(engine, engine.marginal_view, x_local, remote,
-                       src_scale, dst_scale, **_addend_kw(addend, packed))
+            y_m = _agg(engine, engine.marginal_view, xg, remote,
+                       src_scale, dst_scale, **agg_kw)
         y = torch.cat([y_c, y_m], dim=0)
     if add_self:
         y = y + _self_term(engine, x_local, mode)
@@ -262,14 +352,21 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
 
 
 def propagate(engine, x_local: Tensor, layer: int, is_train: bool,
-              mode: PropagationMode, addend=None, packed=None) -> Tensor:
+              mode: PropagationMode, addend=None, packed=None,
+              gather_bf16: Optional[int] = None) -> Tensor:
     """``addend`` ([num_inner, F], the result's dtype): added to the
     aggregation in the SpMM epilogue, before any self term.
     ``packed``: ``pack_rows(x_local)``; the SpMMs gather local rows from
-    it, the exchange still reads the dense ``x_local``."""
+    it, the exchange still reads the dense ``x_local``.
+    ``gather_bf16``: a seed from :func:`next_bwd_gather_seed` (the two
+    backward callers only); the SpMMs gather rows rounded to bf16 with it
+    into the fp32 result. Not combined with ``packed``."""
     key = (f'forward{layer}' if mode == PropagationMode.Forward
            else f'backward{layer}')
     kw = {} if packed is None else {'packed': packed}
+    if gather_bf16 is not None:
+        assert packed is None and x_local.dtype == torch.float32
+        kw['gather_bf16'] = gather_bf16
     if engine.use_parallel:
         return decomposed_propagation(engine, x_local, key, is_train, mode,
                                       addend=addend, **kw)
@@ -294,7 +391,10 @@ class DistAgg(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out: Tensor):
         g = grad_out.to(ctx.engine.compute_dtype).contiguous()
-        gx = propagate(ctx.engine, g, ctx.layer, True, PropagationMode.Backward)
+        seed = next_bwd_gather_seed(ctx.engine, g, ctx.layer)
+        kw = {} if seed is None else {'gather_bf16': seed}
+        gx = propagate(ctx.engine, g, ctx.layer, True,
+                       PropagationMode.Backward, **kw)
         return gx.to(ctx.in_dtype), None, None, None
 
 

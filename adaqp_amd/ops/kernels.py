@@ -321,6 +321,45 @@ def resolve_fused_dequant(flag: Optional[bool]) -> bool:
     return bool(flag)
 
 
+def resolve_bwd_gather_bf16(flag: Optional[bool]) -> bool:
+    """``None`` -> on iff env ``ADAQP_BWD_GATHER_BF16=1``; an explicit bool
+    wins. (``GraphEngine.bwd_gather_bf16`` is the flag; the two backward
+    callers of ``ops/dist_agg.py::propagate`` resolve it at every call.)"""
+    if flag is None:
+        return _os.environ.get('ADAQP_BWD_GATHER_BF16') == '1'
+    return bool(flag)
+
+
+def round_rows_bf16(x: Tensor, seed: int, tag_base: int = 0) -> Tensor:
+    """fp32 [N, F] -> bf16 [N, F] with unbiased stochastic rounding. Element
+    (row, f) with tag ``t = tag_base + row`` draws (u32 arithmetic)
+    ``h = hash_u32(seed ^ (t * 0x9E3779B9) ^ (f * 0x85EBCA6B))``, the integer
+    behind ``quant.uniform_noise``, and keeps the top half of ``b + (h >> 16)``
+    where ``b`` is its bit pattern: the dropped 16 bits round up with
+    probability ``low16 / 2^16``, so ``E[out] = x`` for finite x. Inf and NaN
+    keep their top half (NaN with the quiet bit set). GPU: one pass of the
+    native kernel (csrc/spmm_mixed.hip); CPU: the same definition in torch
+    integer ops, identical bits."""
+    assert x.dtype == torch.float32 and x.dim() == 2
+    x = x.contiguous()
+    if x.is_cuda:
+        return native().round_rows_bf16(x, int(seed) & Q._M32,
+                                        int(tag_base) & Q._M32)
+    N, F = x.shape
+    b = x.view(torch.int32).to(torch.int64) & Q._M32
+    tag = (torch.arange(N, dtype=torch.int64) + int(tag_base)) & Q._M32
+    feat = torch.arange(F, dtype=torch.int64)
+    h = Q._hash_u32((int(seed) & Q._M32)
+                    ^ ((tag[:, None] * 0x9E3779B9) & Q._M32)
+                    ^ ((feat[None, :] * 0x85EBCA6B) & Q._M32))
+    special = (b & 0x7F800000) == 0x7F800000
+    quiet = torch.where((b & 0x007FFFFF) != 0, 0x0040, 0)
+    out = torch.where(special, (b >> 16) | quiet, (b + (h >> 16)) >> 16)
+    # two's-complement wrap into int16, then reinterpret as bf16
+    out = torch.where(out >= 0x8000, out - 0x10000, out).to(torch.int16)
+    return out.view(torch.bfloat16)
+
+
 class QuantRemote:
     """The remote block of one quantized exchange, left in wire form: the
     received ``payload`` (uint8 [plan.total_bytes]) and ``params`` (bf16
@@ -397,7 +436,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
          out: Optional[Tensor] = None, addend: Optional[Tensor] = None,
          wave_index: Optional[bool] = None,
          packed: Union[PackedRows, 'PackedRowsBf16', None] = None,
-         packed_depth: Optional[int] = None) -> Tensor:
+         packed_depth: Optional[int] = None,
+         out_dtype: Optional[torch.dtype] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
     Columns < len(x_local) read x_local; the rest read x_remote (the
@@ -422,7 +462,15 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     combined, and the quantized one wins. Otherwise (CPU, bf16) the block
     is dequantized first and the call proceeds as with a tensor: under
     bf16 it is the dense remote operand of a packed call.
+    ``out_dtype=torch.float32`` with a bf16 ``x_local`` is the mixed call
+    (csrc/spmm_mixed.hip): ``x_remote`` is bf16 (or None, or a QuantRemote,
+    which is dequantized into a bf16 block), ``out`` and ``addend`` are
+    fp32 and ``packed`` must be None. The rows are only gathered in bf16;
+    the result equals ``spmm`` on the widened operands bit for bit.
     """
+    if out_dtype is not None:
+        return _spmm_mixed(view, x_local, x_remote, src_scale, dst_scale,
+                           out, addend, packed, out_dtype)
     indptr, indices, num_rows = view.indptr, view.indices, view.nrows
     quant = None
     if isinstance(x_remote, QuantRemote):
@@ -488,6 +536,48 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
         out.copy_(y)
         return out
     return y
+
+
+def _spmm_mixed(view: 'SpmmView', x_local: Tensor, x_remote, src_scale,
+                dst_scale, out, addend, packed, out_dtype) -> Tensor:
+    """:func:`spmm` with ``out_dtype``: bf16 rows in, fp32 out."""
+    assert out_dtype == torch.float32 and x_local.dtype == torch.bfloat16, \
+        'the mixed spmm gathers bf16 rows into an fp32 result'
+    assert packed is None, 'the mixed spmm takes no packed operand'
+    assert x_local.shape[1] % 2 == 0, 'the mixed spmm needs an even F'
+    if isinstance(x_remote, QuantRemote):
+        x_remote = x_remote.dequantize(torch.bfloat16)
+    if x_remote is not None and not x_remote.numel():
+        x_remote = None
+    assert x_remote is None or x_remote.dtype == torch.bfloat16
+    for t in (out, addend):
+        assert t is None or t.dtype == torch.float32
+    if not x_local.is_cuda:
+        return spmm(view, x_local.float(),
+                    None if x_remote is None else x_remote.float(),
+                    src_scale, dst_scale, out=out, addend=addend)
+    num_rows, F = view.nrows, x_local.shape[1]
+    assert view.max_col < x_local.shape[0] + (
+        0 if x_remote is None else x_remote.shape[0]), \
+        'the view names a column past the rows given'
+    if out is None:
+        out = torch.empty(num_rows, F, dtype=torch.float32,
+                          device=x_local.device)
+    else:
+        assert out.is_contiguous() and out.shape == (num_rows, F)
+    assert addend is None or (addend.is_contiguous()
+                              and addend.shape == out.shape)
+    empty = torch.empty(0, device=x_local.device)
+    native().spmm_csr_bf16in(view.indices, x_local.contiguous(),
+                             x_remote.contiguous() if x_remote is not None
+                             else empty, out,
+                             src_scale if src_scale is not None else empty,
+                             dst_scale if dst_scale is not None else empty,
+                             view.seg_row, view.seg_e0, view.seg_e1,
+                             view.seg_part, view.zero_rows, view.part_ptr,
+                             view.n_part,
+                             addend if addend is not None else empty)
+    return out
 
 
 # --------------------------------------------------------------------------

@@ -53,6 +53,12 @@ class GraphEngine:
         # dequantized block (GPU fp32; ops/dist_agg.py). None: on iff env
         # ADAQP_FUSED_DEQUANT=1, read at each propagation; a bool wins.
         self.fused_dequant: Optional[bool] = None
+        # fp32 backward aggregations gather stochastically rounded bf16 rows
+        # (ops/dist_agg.py). None: on iff env ADAQP_BWD_GATHER_BF16=1, read at
+        # each backward; a bool wins. The rounding seeds come from a counter
+        # of their own, so next_seed()'s stream is the same on and off.
+        self.bwd_gather_bf16: Optional[bool] = None
+        self.bwd_gather_calls = 0
         self.timer = Timer(enabled=False, cuda=self.device.type == 'cuda',
                            mode='events')
         self.is_tracing = False

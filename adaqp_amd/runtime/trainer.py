@@ -61,6 +61,8 @@ class Trainer:
             rt['fused_loss'] = True
         if getattr(args, 'fused_dequant', False):
             rt['fused_dequant'] = True
+        if getattr(args, 'bwd_gather_bf16', False):
+            rt['bwd_gather_bf16'] = True
         self.mode = RunMode(args.mode)
         self.model_type = MODEL_MAP[args.model_name]
         self.comm = Communicator(backend=getattr(args, 'backend', None),
@@ -141,6 +143,7 @@ class Trainer:
                                   msg_dims, agg_type=m['aggregator_type'],
                                   device=self.comm.device)
         self.engine.fused_dequant = self.cfg['runtime'].get('fused_dequant')
+        self.engine.bwd_gather_bf16 = self.cfg['runtime'].get('bwd_gather_bf16')
         if getattr(self.args, 'time_breakdown', False):
             self.engine.timer.enabled = True
         if getattr(self.args, 'dtype', 'fp32') == 'bf16':

@@ -63,6 +63,11 @@ def build_parser() -> argparse.ArgumentParser:
                         'buffer, GPU fp32 (sets runtime.fused_dequant; '
                         'ADAQP_FUSED_DEQUANT=1 is the env switch when neither '
                         'sets it)')
+    p.add_argument('--bwd_gather_bf16', action='store_true',
+                   help='fp32 backward SpMMs gather rows rounded to bf16 '
+                        'without bias (sets runtime.bwd_gather_bf16; '
+                        'ADAQP_BWD_GATHER_BF16=1 is the env switch when '
+                        'neither sets it)')
     return p
 
 

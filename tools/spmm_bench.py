@@ -14,7 +14,11 @@ dense one (fp32 with F % 4 == 0 or ``--dtype bf16`` with F % 8 == 0,
 F <= 256), once per ``--density``: the input
 is synthetic, zeros placed i.i.d. per element, and the pack kernel is timed
 on its own. ``--packed-depth 4,8`` adds one packed variant per number of
-row fetches in flight."""
+row fetches in flight.
+
+``--gather-bf16`` times the fp32 dense kernel against the bf16-gather path
+of the fp32 backward (``round_rows_bf16`` plus the mixed SpMM, with an fp32
+addend), alternated call by call on the same view."""
 import argparse
 import os
 import statistics
@@ -63,6 +67,10 @@ def main():
     p.add_argument('--packed-depth', type=str, default='4',
                    help='row fetches in flight in the packed kernel (4, 8 '
                         'or "4,8")')
+    p.add_argument('--gather-bf16', action='store_true',
+                   help='fp32 dense kernel against the stochastic-rounding '
+                        'cast plus the bf16-gather kernel, alternated call '
+                        'by call (fp32 only)')
     args = p.parse_args()
     assert torch.cuda.is_available()
     from adaqp_amd.ops.kernels import SpmmView, spmm, native
@@ -81,6 +89,10 @@ def main():
 
     if args.packed is not None:
         packed_bench(args, view, x, src, dst, E, head)
+        return
+
+    if args.gather_bf16:
+        gather_bf16_bench(args, view, x, src, dst, head)
         return
 
     if args.wave_index is None or ',' not in args.wave_index:
@@ -186,6 +198,50 @@ def packed_bench(args, view, x, src, dst, E, head):
             print(f'  {name}: {_fmt(times[v])}')
         sys.stdout.flush()
         del xd, pk, outs
+
+
+def gather_bf16_bench(args, view, x, src, dst, head):
+    """fp32 dense SpMM against round_rows_bf16 + the mixed SpMM on the same
+    view, with an fp32 addend as the SAGE backward has one."""
+    from adaqp_amd.ops.kernels import round_rows_bf16, spmm
+    assert x.dtype == torch.float32 and args.F % 2 == 0
+    addend = torch.randn(args.rows, args.F, device=x.device)
+
+    def dense():
+        return spmm(view, x, None, src, dst, addend=addend)
+
+    def cast():
+        return round_rows_bf16(x, 1234)
+
+    def mixed(xb):
+        return spmm(view, xb, None, src, dst, addend=addend,
+                    out_dtype=torch.float32)
+
+    for _ in range(3):
+        yd, xb = dense(), cast()
+        ym = mixed(xb)
+    torch.cuda.synchronize()
+    same = torch.equal(ym, spmm(view, xb.float(), None, src, dst, addend=addend))
+    err = float((ym - yd).abs().max() / yd.abs().max())
+    print(f'{head}: bf16-gather output equals the fp32 kernel on the widened '
+          f'rows: {same}; max |mixed - fp32| / max |fp32| = {err:.3e}')
+    td, tc, tm = [], [], []
+    for _ in range(args.iters):
+        td.append(_timed(dense)[0])
+        t, xb = _timed(cast)
+        tc.append(t)
+        tm.append(_timed(lambda: mixed(xb))[0])
+    E = int(view.indices.numel())
+    print(f'  fp32 dense:       {_fmt(td)}, apparent gather '
+          f'{E * (args.F * 4 + 12) / (statistics.median(td) * 1e-3) / 1e12:.2f} TB/s')
+    print(f'  cast (SR, bf16):  {_fmt(tc)}, '
+          f'{x.numel() * 6 / (statistics.median(tc) * 1e-3) / 1e12:.2f} TB/s '
+          f'read + written')
+    print(f'  bf16 gather:      {_fmt(tm)}, apparent gather '
+          f'{E * (args.F * 2 + 12) / (statistics.median(tm) * 1e-3) / 1e12:.2f} TB/s')
+    print(f'  cast + bf16 gather, sum of medians: '
+          f'{statistics.median(tc) + statistics.median(tm):.3f} ms')
+    sys.stdout.flush()
 
 
 if __name__ == '__main__':
