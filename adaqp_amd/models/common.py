@@ -31,6 +31,11 @@ AGG0_CACHE_DEFAULT = '1'
 # ADAQP_SPMM_PACKED_BF16=1: a bf16 engine packs too (csrc/spmm_packed_bf16.hip).
 # It has an effect only where ADAQP_SPMM_PACKED is on.
 SPMM_PACKED_BF16_DEFAULT = '0'
+# ADAQP_BWD_SKIP_ZERO=0/1: the output layer's backward SpMM skips the rows of
+# its operand that are all zero (nodes outside the train mask). Same bits
+# either way; profiles/spmm_rowskip_NOTES.md has the measurement behind the
+# default.
+BWD_SKIP_ZERO_DEFAULT = '1'
 
 
 def spmm_packed_bf16_on() -> bool:
@@ -233,12 +238,20 @@ class _SageMeanFn(torch.autograd.Function):
     packed, except that with ADAQP_SPMM_PACKED_BF16=1 a bf16 one goes
     through ``pack_rows_bf16``. The backward SpMM gathers a dense GEMM
     output and never is; with ADAQP_BWD_GATHER_BF16=1 an fp32 engine
-    gathers it rounded to bf16 instead (ops/dist_agg.py)."""
+    gathers it rounded to bf16 instead (ops/dist_agg.py).
+
+    ``sparse_grad``: the caller expects whole rows of the upstream gradient
+    to be zero (the output layer under a masked loss: every node outside the
+    train mask). The same rows of ``g @ W_neigh^T`` are then zero, and with
+    ADAQP_BWD_SKIP_ZERO on an fp32 GPU engine marks them in one pass
+    (``row_live``) and the backward SpMM does not fetch them: same bits,
+    fewer bytes. The marks come from the data, so a wrong hint only costs
+    the pass. Not combined with the bf16 gather, which wins."""
 
     @staticmethod
     def forward(ctx, x: Tensor, w1: Tensor, w2: Tensor, b1: Tensor,
                 b2: Tensor, engine, layer: int, is_train: bool,
-                pack: bool = False) -> Tensor:
+                pack: bool = False, sparse_grad: bool = False) -> Tensor:
         from ..ops.dist_agg import propagate
         from ..ops.kernels import pack_rows, pack_rows_bf16
         from ..helpers import PropagationMode
@@ -258,12 +271,14 @@ class _SageMeanFn(torch.autograd.Function):
         xs = x[:num_inner].to(w1.dtype)
         ctx.engine, ctx.layer, ctx.in_dtype = engine, layer, x.dtype
         ctx.in_rows = x.shape[0]
+        ctx.sparse_grad = bool(sparse_grad)
         ctx.save_for_backward(xs, h, w1, w2)
         return torch.addmm(b1, xs, w1) + torch.addmm(b2, h, w2)
 
     @staticmethod
     def backward(ctx, g: Tensor):
         from ..ops.dist_agg import propagate, next_bwd_gather_seed
+        from ..ops.kernels import resolve_bwd_skip_zero, row_live
         from ..helpers import PropagationMode
         xs, h, w1, w2 = ctx.saved_tensors
         engine = ctx.engine
@@ -277,6 +292,16 @@ class _SageMeanFn(torch.autograd.Function):
             # rounded to bf16; addend and result stay fp32
             seed = next_bwd_gather_seed(engine, gh, ctx.layer)
             kw = {} if seed is None else {'gather_bf16': seed}
+            # ADAQP_BWD_SKIP_ZERO (output layer, fp32 engines on the GPU):
+            # the SpMM does not fetch the rows of gh that are all zero
+            if (ctx.sparse_grad and seed is None and gh.is_cuda
+                    and engine.compute_dtype == torch.float32
+                    and gh.dtype == torch.float32 and gh.shape[0] > 0
+                    and resolve_bwd_skip_zero(
+                        getattr(engine, 'bwd_skip_zero', None),
+                        BWD_SKIP_ZERO_DEFAULT)):
+                kw = {'live': row_live(gh)}
+                engine.bwd_skip_hits = getattr(engine, 'bwd_skip_hits', 0) + 1
             if gx_self.dtype == gh.dtype == ctx.in_dtype:
                 gx = propagate(engine, gh, ctx.layer, True,
                                PropagationMode.Backward, addend=gx_self, **kw)
@@ -289,17 +314,19 @@ class _SageMeanFn(torch.autograd.Function):
         gw2 = h.t() @ g if ctx.needs_input_grad[2] else None
         gb = bias_grad(g) if (ctx.needs_input_grad[3]
                            or ctx.needs_input_grad[4]) else None
-        return gx, gw1, gw2, gb, gb, None, None, None, None
+        return gx, gw1, gw2, gb, gb, None, None, None, None, None
 
 
 def sage_mean_layer(engine, x: Tensor, lin1: 'FastLinear', lin2: 'FastLinear',
-                    layer: int, is_train: bool, pack: bool = False) -> Tensor:
+                    layer: int, is_train: bool, pack: bool = False,
+                    sparse_grad: bool = False) -> Tensor:
     """lin1(x[:num_inner]) + lin2(mean aggregation of x) through
     :class:`_SageMeanFn`; weight/bias casts mirror FastLinear.forward.
-    ``pack``: hint that x is mostly zeros (see :class:`_SageMeanFn`)."""
+    ``pack``: hint that x is mostly zeros; ``sparse_grad``: hint that whole
+    rows of the upstream gradient are zero (see :class:`_SageMeanFn`)."""
     w1, w2, b1, b2 = lin1.weight, lin2.weight, lin1.bias, lin2.bias
     if torch.is_autocast_enabled('cuda') and x.is_cuda:
         dt = torch.get_autocast_dtype('cuda')
         w1, w2, b1, b2 = w1.to(dt), w2.to(dt), b1.to(dt), b2.to(dt)
     return _SageMeanFn.apply(x, w1, w2, b1, b2, engine, layer, is_train,
-                             bool(pack))
+                             bool(pack), bool(sparse_grad))

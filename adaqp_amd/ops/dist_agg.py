@@ -144,12 +144,15 @@ def _scales(engine, mode: PropagationMode) -> Tuple[Optional[Tensor], Optional[T
 
 
 def _agg(engine, view, x_local: Tensor, x_remote, src_scale, dst_scale,
-         out=None, addend=None, packed=None, out_dtype=None) -> Tensor:
+         out=None, addend=None, packed=None, out_dtype=None,
+         live=None) -> Tensor:
     """SpMM over one SpmmView. src_scale is the full [N] vector; dst_scale
     and the optional [num_inner, F] addend are sliced to the view's row
     range. ``packed``: ``pack_rows(x_local)`` (the gather's source rows, so
     the same handle serves every view). ``out_dtype``: the mixed call, bf16
-    rows gathered into an fp32 result."""
+    rows gathered into an fp32 result. ``live``: ``row_live(x_local)``, one
+    array of the local rows for every view; all-zero local rows are not
+    fetched."""
     ds = (dst_scale[view.base:view.base + view.nrows]
           if dst_scale is not None else None)
     ad = (addend[view.base:view.base + view.nrows]
@@ -159,18 +162,24 @@ def _agg(engine, view, x_local: Tensor, x_remote, src_scale, dst_scale,
         return spmm(view, x_local, x_remote, src_scale, ds, out=out,
                     addend=ad, out_dtype=out_dtype)
     if packed is not None:
+        assert live is None
         return spmm(view, x_local, x_remote, src_scale, ds, out=out,
                     addend=ad, packed=packed)
+    if live is not None:
+        return spmm(view, x_local, x_remote, src_scale, ds, out=out,
+                    addend=ad, live=live)
     return spmm(view, x_local, x_remote, src_scale, ds, out=out, addend=ad)
 
 
-def _addend_kw(addend, packed=None) -> dict:
-    """_agg's ``addend`` and ``packed`` keywords, each passed only when
-    there is one, so the plain aggregation keeps the call signature it
+def _addend_kw(addend, packed=None, live=None) -> dict:
+    """_agg's ``addend``, ``packed`` and ``live`` keywords, each passed only
+    when there is one, so the plain aggregation keeps the call signature it
     always had."""
     kw = {} if addend is None else {'addend': addend}
     if packed is not None:
         kw['packed'] = packed
+    if live is not None:
+        kw['live'] = live
     return kw
 
 
@@ -238,7 +247,8 @@ def _self_term(engine, x_local: Tensor, mode: PropagationMode) -> Tensor:
 
 def full_propagation(engine, x_local: Tensor, key: str, is_train: bool,
                      mode: PropagationMode, addend=None,
-                     packed=None, gather_bf16: Optional[int] = None) -> Tensor:
+                     packed=None, gather_bf16: Optional[int] = None,
+                     live=None) -> Tensor:
     quant = engine.bit_type == BitType.QUANT and is_train
     if _fused_dequant(engine, x_local, key, quant):
         remote = _exchange_finish(
@@ -261,7 +271,7 @@ def full_propagation(engine, x_local: Tensor, key: str, is_train: bool,
                      out_dtype=torch.float32)
         else:
             y = _agg(engine, engine.full_view, x_local, remote, src_scale,
-                     dst_scale, **_addend_kw(addend, packed))
+                     dst_scale, **_addend_kw(addend, packed, live))
         if add_self:
             y = y + _self_term(engine, x_local, mode)
     return y
@@ -270,7 +280,8 @@ def full_propagation(engine, x_local: Tensor, key: str, is_train: bool,
 def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
                            mode: PropagationMode, addend=None,
                            packed=None,
-                           gather_bf16: Optional[int] = None) -> Tensor:
+                           gather_bf16: Optional[int] = None,
+                           live=None) -> Tensor:
     """Central aggregation (default stream) overlapped with
     quant->all_to_all->dequant (comm stream).
 
@@ -291,7 +302,7 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
     # the exchange and the self term keep reading the fp32 x_local
     bf16 = gather_bf16 is not None
     agg_kw = ({'addend': addend, 'out_dtype': torch.float32} if bf16
-              else _addend_kw(addend, packed))
+              else _addend_kw(addend, packed, live))
     deq_kw = {'remote_dtype': torch.bfloat16} if bf16 and quant else {}
     xg = x_local
 
@@ -353,17 +364,23 @@ def decomposed_propagation(engine, x_local: Tensor, key: str, is_train: bool,
 
 def propagate(engine, x_local: Tensor, layer: int, is_train: bool,
               mode: PropagationMode, addend=None, packed=None,
-              gather_bf16: Optional[int] = None) -> Tensor:
+              gather_bf16: Optional[int] = None, live=None) -> Tensor:
     """``addend`` ([num_inner, F], the result's dtype): added to the
     aggregation in the SpMM epilogue, before any self term.
     ``packed``: ``pack_rows(x_local)``; the SpMMs gather local rows from
     it, the exchange still reads the dense ``x_local``.
     ``gather_bf16``: a seed from :func:`next_bwd_gather_seed` (the two
     backward callers only); the SpMMs gather rows rounded to bf16 with it
-    into the fp32 result. Not combined with ``packed``."""
+    into the fp32 result. Not combined with ``packed``.
+    ``live``: ``row_live(x_local)`` (GPU fp32); the SpMMs do not fetch the
+    local rows it marks as all zero, the exchange still reads the dense
+    ``x_local``. Not combined with ``packed`` or ``gather_bf16``."""
     key = (f'forward{layer}' if mode == PropagationMode.Forward
            else f'backward{layer}')
     kw = {} if packed is None else {'packed': packed}
+    if live is not None:
+        assert packed is None and gather_bf16 is None
+        kw['live'] = live
     if gather_bf16 is not None:
         assert packed is None and x_local.dtype == torch.float32
         kw['gather_bf16'] = gather_bf16

@@ -360,6 +360,28 @@ def round_rows_bf16(x: Tensor, seed: int, tag_base: int = 0) -> Tensor:
     return out.view(torch.bfloat16)
 
 
+def resolve_bwd_skip_zero(flag: Optional[bool], default: str) -> bool:
+    """``None`` -> env ``ADAQP_BWD_SKIP_ZERO`` (``default`` when unset) is
+    '1'; an explicit bool wins. (``GraphEngine.bwd_skip_zero`` is the flag;
+    models/common.py resolves it at every output-layer backward.)"""
+    if flag is None:
+        return _os.environ.get('ADAQP_BWD_SKIP_ZERO', default) == '1'
+    return bool(flag)
+
+
+def row_live(x: Tensor) -> Tensor:
+    """uint8 [N] for an fp32 [N, F] tensor: 1 where the row holds an element
+    of non-zero magnitude, by bit pattern (``bits & 0x7fffffff != 0``), so
+    denormals, NaN and Inf count and -0.0 does not. GPU: one pass of the
+    native kernel (csrc/spmm_rowskip.hip); CPU: the same definition in torch
+    integer ops. The ``live=`` operand of :func:`spmm`."""
+    assert x.dtype == torch.float32 and x.dim() == 2
+    x = x.contiguous()
+    if x.is_cuda:
+        return native().row_live(x)
+    return ((x.view(torch.int32) & 0x7FFFFFFF) != 0).any(dim=1).to(torch.uint8)
+
+
 class QuantRemote:
     """The remote block of one quantized exchange, left in wire form: the
     received ``payload`` (uint8 [plan.total_bytes]) and ``params`` (bf16
@@ -437,7 +459,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
          wave_index: Optional[bool] = None,
          packed: Union[PackedRows, 'PackedRowsBf16', None] = None,
          packed_depth: Optional[int] = None,
-         out_dtype: Optional[torch.dtype] = None) -> Tensor:
+         out_dtype: Optional[torch.dtype] = None,
+         live: Optional[Tensor] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
     Columns < len(x_local) read x_local; the rest read x_remote (the
@@ -467,7 +490,15 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     which is dequantized into a bf16 block), ``out`` and ``addend`` are
     fp32 and ``packed`` must be None. The rows are only gathered in bf16;
     the result equals ``spmm`` on the widened operands bit for bit.
+    ``live``: ``row_live(x_local)`` (GPU fp32 only); local rows it marks as
+    all zero are not fetched (csrc/spmm_rowskip.hip), same result bit for
+    bit. A 0 for a row that holds a non-zero is a misuse: that row is then
+    read as zeros. Not combined with ``packed`` or ``out_dtype``; with a
+    fusable ``QuantRemote`` the quantized-gather kernel runs and ``live`` is
+    not used for that call. Ignored on the CPU.
     """
+    assert live is None or (packed is None and out_dtype is None), \
+        'live is not combined with packed or out_dtype'
     if out_dtype is not None:
         return _spmm_mixed(view, x_local, x_remote, src_scale, dst_scale,
                            out, addend, packed, out_dtype)
@@ -478,7 +509,7 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
             assert x_remote.F == x_local.shape[1]
             assert view.max_col < x_local.shape[0] + x_remote.rows, \
                 'the view names a column past the remote rows described'
-            quant, x_remote, packed = x_remote, None, None
+            quant, x_remote, packed, live = x_remote, None, None, None
         else:
             x_remote = x_remote.dequantize(x_local.dtype)
     if not x_local.is_cuda and view.col_blocked:
@@ -498,6 +529,21 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
         if packed is not None:
             assert packed.matches(x_local), \
                 'packed operand was not made from x_local'
+        if live is not None and x_local.shape[0] > 0:
+            assert x_local.dtype == torch.float32, \
+                'the row-skipping spmm is fp32 only'
+            assert (live.dtype == torch.uint8
+                    and live.shape == (x_local.shape[0],)), \
+                'live operand was not made from x_local'
+            native().spmm_csr_rowskip(
+                indices, x_local,
+                x_remote if x_remote is not None else empty, out,
+                src_scale if src_scale is not None else empty,
+                dst_scale if dst_scale is not None else empty,
+                view.seg_row, view.seg_e0, view.seg_e1, view.seg_part,
+                view.zero_rows, view.part_ptr, view.n_part,
+                addend if addend is not None else empty, live)
+            return out
         native().spmm_csr(indices, x_local,
                           x_remote if x_remote is not None else empty, out,
                           src_scale if src_scale is not None else empty,

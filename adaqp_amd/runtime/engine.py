@@ -59,6 +59,12 @@ class GraphEngine:
         # of their own, so next_seed()'s stream is the same on and off.
         self.bwd_gather_bf16: Optional[bool] = None
         self.bwd_gather_calls = 0
+        # the output layer's backward SpMM does not fetch all-zero gradient
+        # rows (models/common.py). None: env ADAQP_BWD_SKIP_ZERO, else the
+        # default there, read at each backward; a bool wins. bwd_skip_hits
+        # counts the backward SpMMs that took the row-skipping path.
+        self.bwd_skip_zero: Optional[bool] = None
+        self.bwd_skip_hits = 0
         self.timer = Timer(enabled=False, cuda=self.device.type == 'cuda',
                            mode='events')
         self.is_tracing = False

@@ -18,7 +18,12 @@ row fetches in flight.
 
 ``--gather-bf16`` times the fp32 dense kernel against the bf16-gather path
 of the fp32 backward (``round_rows_bf16`` plus the mixed SpMM, with an fp32
-addend), alternated call by call on the same view."""
+addend), alternated call by call on the same view.
+
+``--zero-rows 0,0.34,0.92`` times the fp32 dense kernel against ``row_live``
+plus the row-skipping kernel (the output layer's backward), once per fraction
+of all-zero rows, alternated call by call with an fp32 addend, after checking
+that the two give the same bits."""
 import argparse
 import os
 import statistics
@@ -71,6 +76,10 @@ def main():
                    help='fp32 dense kernel against the stochastic-rounding '
                         'cast plus the bf16-gather kernel, alternated call '
                         'by call (fp32 only)')
+    p.add_argument('--zero-rows', type=str, default=None,
+                   help='fractions of all-zero rows, e.g. "0,0.34,0.92": fp32 '
+                        'dense kernel against row_live plus the row-skipping '
+                        'kernel, alternated call by call')
     args = p.parse_args()
     assert torch.cuda.is_available()
     from adaqp_amd.ops.kernels import SpmmView, spmm, native
@@ -93,6 +102,10 @@ def main():
 
     if args.gather_bf16:
         gather_bf16_bench(args, view, x, src, dst, head)
+        return
+
+    if args.zero_rows is not None:
+        zero_rows_bench(args, view, x, src, dst, head)
         return
 
     if args.wave_index is None or ',' not in args.wave_index:
@@ -242,6 +255,53 @@ def gather_bf16_bench(args, view, x, src, dst, head):
     print(f'  cast + bf16 gather, sum of medians: '
           f'{statistics.median(tc) + statistics.median(tm):.3f} ms')
     sys.stdout.flush()
+
+
+def zero_rows_bench(args, view, x, src, dst, head):
+    """fp32 dense SpMM against row_live + the row-skipping SpMM on the same
+    view, with an fp32 addend as the SAGE backward has one; rows are zeroed
+    i.i.d. with each given probability."""
+    from adaqp_amd.ops.kernels import row_live, spmm
+    assert x.dtype == torch.float32
+    addend = torch.randn(args.rows, args.F, device=x.device)
+    gen = torch.Generator(device=x.device).manual_seed(11)
+    E = int(view.indices.numel())
+    for frac in [float(f) for f in args.zero_rows.split(',')]:
+        keep = torch.rand(x.shape[0], device=x.device, generator=gen) >= frac
+        xz = (x * keep[:, None]).contiguous()
+
+        def dense():
+            return spmm(view, xz, None, src, dst, addend=addend)
+
+        def mark():
+            return row_live(xz)
+
+        def skip(live):
+            return spmm(view, xz, None, src, dst, addend=addend, live=live)
+
+        for _ in range(3):
+            yd, live = dense(), mark()
+            ys = skip(live)
+        torch.cuda.synchronize()
+        same = torch.equal(ys.view(torch.int32), yd.view(torch.int32))
+        dead = 1.0 - float(live.float().mean())
+        print(f'{head} zero rows {frac} (marked dead {dead:.3f}): outputs of '
+              f'dense and row-skipping bit-identical: {same}')
+        td, tl, ts = [], [], []
+        for _ in range(args.iters):
+            td.append(_timed(dense)[0])
+            t, live = _timed(mark)
+            tl.append(t)
+            ts.append(_timed(lambda: skip(live))[0])
+        print(f'  fp32 dense:   {_fmt(td)}, apparent gather '
+              f'{E * (args.F * 4 + 12) / (statistics.median(td) * 1e-3) / 1e12:.2f} TB/s')
+        print(f'  row_live:     {_fmt(tl)}, '
+              f'{xz.numel() * 4 / (statistics.median(tl) * 1e-3) / 1e12:.2f} TB/s read')
+        print(f'  row-skipping: {_fmt(ts)}')
+        print(f'  row_live + row-skipping, sum of medians: '
+              f'{statistics.median(tl) + statistics.median(ts):.3f} ms')
+        sys.stdout.flush()
+        del xz, keep, yd, ys, live
 
 
 if __name__ == '__main__':
