@@ -64,6 +64,51 @@ __device__ __forceinline__ T round_add(float o, const T* ad) {
 }
 
 
+// Ordered sweep over the segment array (launch parameter order == 1 of
+// spmm_csr_kernel, spmm_packed_*_kernel and spmm_rowskip_kernel). The static
+// order hands block b the segments b, b + grid, b + 2 grid, ...: with more
+// blocks than are resident the grid passes over the whole graph several
+// times, and the waves running at one instant gather from all over the
+// table. Here the grid is the resident block count and every wavefront
+// repeatedly takes a ticket t from one counter (zeroed before the launch)
+// and processes segments [t * chunk, (t + 1) * chunk): the whole GPU moves
+// through the rows once, front to back, so the rows gathered at one instant
+// are those of neighbouring segments. No wave waits for another; a wave
+// leaves when its ticket is past the last segment.
+//
+// Returns the first segment of the calling wave's next chunk (wave-uniform).
+// Every lane of the wave that is still running must call it together, lane 0
+// among them.
+__device__ __forceinline__ int64_t next_chunk(int32_t* ticket, int chunk) {
+    int t = 0;
+    if ((threadIdx.x & (WAVE - 1)) == 0) t = atomicAdd(ticket, 1);
+    t = __builtin_amdgcn_readfirstlane(t);
+    // The broadcast value is moved back to a vector register on purpose.
+    // Told that the segment index is uniform, the compiler turns the whole
+    // index path of the one-wavefront-per-segment kernels into scalar code
+    // and their 106 SGPRs cap occupancy at 7 waves/SIMD; this way the
+    // segment body compiles as under the static order and keeps its 8.
+    asm volatile("" : "+v"(t));
+    return (int64_t)t * chunk;
+}
+
+// Grid of an ordered launch: the blocks of `threads` threads of `kernel`
+// that are resident at once on the current device, capped by the blocks the
+// segments need.
+template <typename K>
+static inline unsigned ordered_grid(K kernel, int threads, int64_t blocks_needed) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, reinterpret_cast<const void*>(kernel), threads, 0) != hipSuccess ||
+        cus < 1 || per_cu < 1)
+        return 0;       // the caller reports it
+    const int64_t resident = (int64_t)cus * per_cu;
+    return (unsigned)(blocks_needed < resident ? (blocks_needed < 1 ? 1 : blocks_needed)
+                                               : resident);
+}
+
 // raw load/store type of NB bytes
 template <int NB> struct RawVec;
 template <> struct RawVec<16> { using type = uint4; };

@@ -235,7 +235,9 @@ __global__ void combine_parts_kernel(T* __restrict__ y,
 // VE = elements per lane per load; chosen host-side as the largest of
 // {8,4,2}(bf16) / {4,2,1}(f32) dividing F, so every row-base load of
 // width VE*sizeof(T) is aligned (rows are x + c*F*sizeof(T)).
-template <int SW, typename T, int VE>
+// ORD: the segments are handed out by the ordered sweep (launch parameter
+// order == 1) instead of the static swizzle plus grid stride.
+template <int SW, typename T, int VE, bool ORD>
 __global__ void spmm_csr_kernel(
     const int32_t* __restrict__ indices,   // int32: halves index bytes
     const T* __restrict__ xl, const T* __restrict__ xr,
@@ -244,7 +246,8 @@ __global__ void spmm_csr_kernel(
     const int32_t* __restrict__ seg_row, const int32_t* __restrict__ seg_e0,
     const int32_t* __restrict__ seg_e1, const int32_t* __restrict__ seg_part,
     float* __restrict__ part, const T* __restrict__ addend,
-    int64_t n_seg, int64_t F, int64_t n_local) {
+    int64_t n_seg, int64_t F, int64_t n_local,
+    int chunk, int32_t* __restrict__ ticket) {
     constexpr int NB = VE * sizeof(T);
     using Raw = typename RawVec<NB>::type;
     const int rows_per_block = blockDim.x / SW;
@@ -256,8 +259,16 @@ __global__ void spmm_csr_kernel(
     const int64_t sub0 = swz * rows_per_block + threadIdx.x / SW;
     const int64_t stride = nwg * rows_per_block;
     const int sl = threadIdx.x & (SW - 1);
-
-    for (int64_t it = sub0; it < n_seg; it += stride) {
+    // !ORD: one pass of the static grid-stride loop. ORD (ordered
+    // sweep, next_chunk in device_common.h): the wave takes chunks of
+    // segments until none is left, its sub-wavefronts interleaving over
+    // each. The segment body is the same.
+    const int wsub = (threadIdx.x & (WAVE - 1)) / SW;
+    for (int64_t c0 = ORD ? next_chunk(ticket, chunk) : 0; c0 < n_seg;
+         c0 = ORD ? next_chunk(ticket, chunk) : n_seg) {
+    const int64_t c1 = ORD ? min(c0 + chunk, n_seg) : n_seg;
+    for (int64_t it = ORD ? c0 + wsub : sub0; it < c1;
+         it += ORD ? WAVE / SW : stride) {
         const int64_t r = seg_row[it];
         const int64_t e0 = seg_e0[it], e1 = seg_e1[it];
         const int64_t slot = seg_part[it];     // >= 0: row split across segments
@@ -345,6 +356,7 @@ __global__ void spmm_csr_kernel(
                     pp[k] = (acc0[k] + acc1[k]) * ds;
             }
         }
+    }
     }
 }
 
@@ -601,7 +613,8 @@ void launch_spmm_packed(
     const uint8_t* pk, float* y, const float* src_scale,
     const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
     const int32_t* seg_e1, const int32_t* seg_part, float* part,
-    const float* addend, int64_t n_seg, int64_t F, int64_t n_local);
+    const float* addend, int64_t n_seg, int64_t F, int64_t n_local,
+    int order, int chunk, int32_t* ticket);
 // spmm_packed_bf16.hip
 bool spmm_packable_bf16(int64_t F);
 int64_t packed_bf16_meta_bytes(int64_t F);
@@ -643,10 +656,30 @@ void launch_spmm_rowskip(
     const uint8_t* live, float* y, const float* src_scale,
     const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
     const int32_t* seg_e1, const int32_t* seg_part, float* part,
-    const float* addend, int64_t n_seg, int64_t F, int64_t n_local);
+    const float* addend, int64_t n_seg, int64_t F, int64_t n_local,
+    int order, int chunk, int32_t* ticket);
 
 static inline hipStream_t cur_stream() {
     return at::cuda::getCurrentHIPStream().stream();
+}
+
+// Ticket counter of one ordered SpMM launch (next_chunk, device_common.h):
+// one int32 from the caching allocator, so it belongs to the current stream,
+// zeroed there by a one-thread kernel. A call owns its counter; the tensor
+// the caller holds keeps it alive until the launch is queued behind it.
+__global__ void zero_ticket_kernel(int32_t* ticket) { *ticket = 0; }
+
+static torch::Tensor new_ticket(const torch::Tensor& like, hipStream_t s) {
+    torch::Tensor t = torch::empty({1}, like.options().dtype(torch::kInt32));
+    zero_ticket_kernel<<<1, 1, 0, s>>>(t.data_ptr<int32_t>());
+    return t;
+}
+
+static void check_order(int64_t order, int64_t chunk) {
+    TORCH_CHECK(order == 0 || order == 1,
+                "spmm order must be 0 (static) or 1 (ordered sweep)");
+    TORCH_CHECK(chunk >= 1 && chunk <= (1 << 20),
+                "spmm chunk must be between 1 and 2^20 segments");
 }
 
 void quant_pack(torch::Tensor x, torch::Tensor rows, torch::Tensor pos,
@@ -712,7 +745,8 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
               torch::Tensor part_ptr, int64_t n_part,
               torch::Tensor addend, bool wave_index,
               torch::Tensor packed, int64_t packed_depth,
-              torch::Tensor q_payload, torch::Tensor q_desc) {
+              torch::Tensor q_payload, torch::Tensor q_desc,
+              int64_t order, int64_t chunk) {
     CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
     const bool bf16 = xl.scalar_type() == torch::kBFloat16;
     TORCH_CHECK(bf16 || xl.scalar_type() == torch::kFloat32,
@@ -739,6 +773,7 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
         ad_ptr = addend.numel() ? addend.data_ptr() : nullptr;
     }
     auto s = cur_stream();
+    check_order(order, chunk);
     TORCH_CHECK(seg_part.scalar_type() == torch::kInt32 &&
                 seg_part.numel() == n_seg &&
                 zero_rows.scalar_type() == torch::kInt32 &&
@@ -831,6 +866,15 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
         combine();
         return;
     }
+    // the ordered sweep is built into the dense per-lane kernel and the fp32
+    // packed kernels; the kernels above and the wave-index one walk the
+    // static order whatever `order` says
+    torch::Tensor ticket;
+    int32_t* ticket_p = nullptr;
+    if (order) {
+        ticket = new_ticket(xl, s);
+        ticket_p = ticket.data_ptr<int32_t>();
+    }
     if (packed.numel()) {
         CHECK_DEV(packed); CHECK_CONTIG(packed);
         TORCH_CHECK(!bf16 && spmm_packable(F) && n_local > 0,
@@ -844,7 +888,8 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
             reinterpret_cast<const float*>(xr_ptr),
             packed.data_ptr<uint8_t>(), y.data_ptr<float>(), ss_p, ds_p,
             sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(),
-            reinterpret_cast<const float*>(ad_ptr), n_seg, F, n_local);
+            reinterpret_cast<const float*>(ad_ptr), n_seg, F, n_local,
+            (int)order, (int)chunk, ticket_p);
         combine();
         return;
     }
@@ -868,12 +913,27 @@ void spmm_csr(torch::Tensor indices, torch::Tensor xl,
                 return;
             }
         }
-        spmm_csr_kernel<SWC, TC, VEC><<<grid, block, 0, s>>>(
+        if (order) {
+            const dim3 g(ordered_grid(
+                spmm_csr_kernel<SWC, TC, VEC, true>, block_threads,
+                (n_seg + rows_per_block - 1) / rows_per_block));
+            TORCH_CHECK(g.x > 0, "spmm_csr: occupancy query failed");
+            spmm_csr_kernel<SWC, TC, VEC, true><<<g, block, 0, s>>>(
+                ind_p, reinterpret_cast<const TC*>(xl.data_ptr()),
+                reinterpret_cast<const TC*>(xr_ptr),
+                reinterpret_cast<TC*>(y.data_ptr()), ss_p, ds_p,
+                sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(),
+                reinterpret_cast<const TC*>(ad_ptr), n_seg, F, n_local,
+                (int)chunk, ticket_p);
+            return;
+        }
+        spmm_csr_kernel<SWC, TC, VEC, false><<<grid, block, 0, s>>>(
             ind_p, reinterpret_cast<const TC*>(xl.data_ptr()),
             reinterpret_cast<const TC*>(xr_ptr),
             reinterpret_cast<TC*>(y.data_ptr()), ss_p, ds_p,
             sr_p, e0_p, e1_p, sp_p, part.data_ptr<float>(),
-            reinterpret_cast<const TC*>(ad_ptr), n_seg, F, n_local);
+            reinterpret_cast<const TC*>(ad_ptr), n_seg, F, n_local,
+            0, nullptr);
     };
     struct FT { using type = float; };
     struct BT { using type = ushort; };
@@ -1007,7 +1067,7 @@ void spmm_csr_rowskip(torch::Tensor indices, torch::Tensor xl,
                       torch::Tensor seg_e1, torch::Tensor seg_part,
                       torch::Tensor zero_rows, torch::Tensor part_ptr,
                       int64_t n_part, torch::Tensor addend,
-                      torch::Tensor live) {
+                      torch::Tensor live, int64_t order, int64_t chunk) {
     CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
     TORCH_CHECK(xl.dim() == 2 && xl.scalar_type() == torch::kFloat32 &&
                 y.dim() == 2 && y.scalar_type() == torch::kFloat32,
@@ -1080,6 +1140,9 @@ void spmm_csr_rowskip(torch::Tensor indices, torch::Tensor xl,
     auto s = cur_stream();
     torch::Tensor part = torch::empty(
         {n_part, F}, y.options().dtype(torch::kFloat32));
+    check_order(order, chunk);
+    torch::Tensor ticket;
+    if (n_seg && order) ticket = new_ticket(y, s);
     if (n_seg)
         launch_spmm_rowskip(
             s, indices.data_ptr<int32_t>(), xl.data_ptr<float>(), xr_ptr,
@@ -1088,7 +1151,9 @@ void spmm_csr_rowskip(torch::Tensor indices, torch::Tensor xl,
             dst_scale.numel() ? dst_scale.data_ptr<float>() : nullptr,
             seg_row.data_ptr<int32_t>(), seg_e0.data_ptr<int32_t>(),
             seg_e1.data_ptr<int32_t>(), seg_part.data_ptr<int32_t>(),
-            part.data_ptr<float>(), ad_ptr, n_seg, F, n_local);
+            part.data_ptr<float>(), ad_ptr, n_seg, F, n_local,
+            (int)order, (int)chunk,
+            order ? ticket.data_ptr<int32_t>() : nullptr);
     if (zero_rows.numel()) {
         const dim3 zb(256), zg((zero_rows.numel() + 3) / 4);
         combine_parts_kernel<float><<<zg, zb, 0, s>>>(
@@ -1169,7 +1234,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("packed") = torch::Tensor(),
           pybind11::arg("packed_depth") = 4,
           pybind11::arg("q_payload") = torch::Tensor(),
-          pybind11::arg("q_desc") = torch::Tensor());
+          pybind11::arg("q_desc") = torch::Tensor(),
+          pybind11::arg("order") = 0, pybind11::arg("chunk") = 4);
     m.def("spmm_csr_bf16in", &spmm_csr_bf16in,
           "spmm_csr gathering bf16 rows into fp32 accumulators, addend and "
           "output (CDNA4)",
@@ -1197,7 +1263,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("seg_e0"), pybind11::arg("seg_e1"),
           pybind11::arg("seg_part"), pybind11::arg("zero_rows"),
           pybind11::arg("part_ptr"), pybind11::arg("n_part"),
-          pybind11::arg("addend"), pybind11::arg("live"));
+          pybind11::arg("addend"), pybind11::arg("live"),
+          pybind11::arg("order") = 0, pybind11::arg("chunk") = 4);
     m.def("quant_row_desc", &quant_row_desc,
           "per-remote-row {offset, bits, inv, rmin} descriptors of one "
           "quantized exchange, for the quantized-gather SpMM (CDNA4)");

@@ -103,7 +103,7 @@ struct __attribute__((packed, aligned(4))) Win4 { uint32_t w[4]; };
 
 // SS: a src_scale vector is given (a template flag, so that the batch
 // below stays one basic block and its loads are issued together)
-template <int SW, int NE, bool SS>
+template <int SW, int NE, bool SS, bool ORD>
 __global__ void __launch_bounds__(WAVE * 4) spmm_packed_kernel(
     const int32_t* __restrict__ indices,
     const float* __restrict__ xl, const float* __restrict__ xr,
@@ -113,7 +113,8 @@ __global__ void __launch_bounds__(WAVE * 4) spmm_packed_kernel(
     const int32_t* __restrict__ seg_row, const int32_t* __restrict__ seg_e0,
     const int32_t* __restrict__ seg_e1, const int32_t* __restrict__ seg_part,
     float* __restrict__ part, const float* __restrict__ addend,
-    int64_t n_seg, int64_t F, int64_t n_local, int64_t meta, int64_t stride) {
+    int64_t n_seg, int64_t F, int64_t n_local, int64_t meta, int64_t stride,
+    int chunk, int32_t* __restrict__ ticket) {
     constexpr int VE = 4;
     const int rows_per_block = blockDim.x / SW;
     // bijective XCD swizzle, as spmm_csr_kernel
@@ -128,8 +129,15 @@ __global__ void __launch_bounds__(WAVE * 4) spmm_packed_kernel(
     if (f0 >= F) return;
     const uint8_t* pkw = pk + 2 * sl;        // this lane's word in row 0
     const uint8_t* pkv = pk + meta;          // value run of row 0
-
-    for (int64_t it = sub0; it < n_seg; it += step) {
+    // !ORD: one pass of the static grid-stride loop; ORD: the ordered
+    // sweep, as spmm_csr_kernel (next_chunk in device_common.h; lane 0 of a
+    // wave owns feature 0 and is still here)
+    const int wsub = (threadIdx.x & (WAVE - 1)) / SW;
+    for (int64_t c0 = ORD ? next_chunk(ticket, chunk) : 0; c0 < n_seg;
+         c0 = ORD ? next_chunk(ticket, chunk) : n_seg) {
+    const int64_t c1 = ORD ? min(c0 + chunk, n_seg) : n_seg;
+    for (int64_t it = ORD ? c0 + wsub : sub0; it < c1;
+         it += ORD ? WAVE / SW : step) {
         const int64_t r = seg_row[it];
         const int64_t e0 = seg_e0[it], e1 = seg_e1[it];
         const int64_t slot = seg_part[it];
@@ -213,6 +221,7 @@ __global__ void __launch_bounds__(WAVE * 4) spmm_packed_kernel(
                 pp[k] = (acc0[k] + acc1[k]) * ds;
         }
     }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -230,7 +239,7 @@ __device__ __forceinline__ float readlane_f32(float v, int l) {
     return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), l));
 }
 
-template <int NE, bool SS>
+template <int NE, bool SS, bool ORD>
 __global__ void __launch_bounds__(WAVE * 4) spmm_packed_wave_kernel(
     const int32_t* __restrict__ indices,
     const float* __restrict__ xl, const float* __restrict__ xr,
@@ -240,7 +249,8 @@ __global__ void __launch_bounds__(WAVE * 4) spmm_packed_wave_kernel(
     const int32_t* __restrict__ seg_row, const int32_t* __restrict__ seg_e0,
     const int32_t* __restrict__ seg_e1, const int32_t* __restrict__ seg_part,
     float* __restrict__ part, const float* __restrict__ addend,
-    int64_t n_seg, int64_t F, int64_t n_local, int64_t meta, int64_t stride) {
+    int64_t n_seg, int64_t F, int64_t n_local, int64_t meta, int64_t stride,
+    int chunk, int32_t* __restrict__ ticket) {
     constexpr int VE = 4;
     const int waves_per_block = blockDim.x / WAVE;
     const int64_t nwg = gridDim.x;
@@ -259,7 +269,13 @@ __global__ void __launch_bounds__(WAVE * 4) spmm_packed_wave_kernel(
     const uint32_t nl = (uint32_t)n_local, Fu = (uint32_t)F;
     const uint32_t st = (uint32_t)stride, mt = (uint32_t)meta;
 
-    for (int64_t it = swz * waves_per_block + wave; it < n_seg; it += step) {
+    // !ORD: one pass of the static grid-stride loop; ORD: the ordered
+    // sweep, as spmm_csr_kernel (next_chunk in device_common.h)
+    for (int64_t c0 = ORD ? next_chunk(ticket, chunk) : 0; c0 < n_seg;
+         c0 = ORD ? next_chunk(ticket, chunk) : n_seg) {
+    const int64_t c1 = ORD ? min(c0 + chunk, n_seg) : n_seg;
+    for (int64_t it = ORD ? c0 : swz * waves_per_block + wave; it < c1;
+         it += ORD ? 1 : step) {
         const int64_t r = __builtin_amdgcn_readfirstlane(seg_row[it]);
         const int e0 = __builtin_amdgcn_readfirstlane(seg_e0[it]);
         const int e1 = __builtin_amdgcn_readfirstlane(seg_e1[it]);
@@ -355,6 +371,7 @@ __global__ void __launch_bounds__(WAVE * 4) spmm_packed_wave_kernel(
                 pp[k] = (acc0[k] + acc1[k]) * ds;
         }
     }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -408,23 +425,37 @@ void launch_spmm_packed(
     const uint8_t* pk, float* y, const float* src_scale,
     const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
     const int32_t* seg_e1, const int32_t* seg_part, float* part,
-    const float* addend, int64_t n_seg, int64_t F, int64_t n_local) {
+    const float* addend, int64_t n_seg, int64_t F, int64_t n_local,
+    int order, int chunk, int32_t* ticket) {
     TORCH_CHECK(depth == 4 || depth == 8, "packed SpMM depth must be 4 or 8");
     TORCH_CHECK(n_local < (1ll << 31), "packed spmm: n_local must fit 31 bits");
     // SW == 64 runs the wave-uniform kernel, narrower rows the per-lane one
     const int sw = sub_wave(F);
-#define LAUNCH(SWC, NEC, SSC) spmm_packed_kernel<SWC, NEC, SSC><<<grid, block, 0, s>>>( \
-        indices, xl, xr, pk, y, src_scale, dst_scale, seg_row, seg_e0, \
-        seg_e1, seg_part, part, addend, n_seg, F, n_local, \
-        pack_meta_bytes(F), pack_stride(F))
+    // order 1: the resident blocks of the instantiation (ordered_grid) in
+    // place of the caller's static grid
+    const int64_t per_block = block.x / sw;
+    const int64_t needed = (n_seg + per_block - 1) / per_block;
+#define LAUNCH_O(KERNEL, ORDC, ...) do { \
+        dim3 g = grid; \
+        if (ORDC) { \
+            g = dim3(ordered_grid(KERNEL<__VA_ARGS__, ORDC>, (int)block.x, needed)); \
+            TORCH_CHECK(g.x > 0, "packed spmm: occupancy query failed"); \
+        } \
+        KERNEL<__VA_ARGS__, ORDC><<<g, block, 0, s>>>( \
+            indices, xl, xr, pk, y, src_scale, dst_scale, seg_row, seg_e0, \
+            seg_e1, seg_part, part, addend, n_seg, F, n_local, \
+            pack_meta_bytes(F), pack_stride(F), chunk, ticket); \
+    } while (0)
+#define LAUNCH_K(KERNEL, ...) do { \
+        if (order) LAUNCH_O(KERNEL, true, __VA_ARGS__); \
+        else LAUNCH_O(KERNEL, false, __VA_ARGS__); \
+    } while (0)
+#define LAUNCH(SWC, NEC, SSC) LAUNCH_K(spmm_packed_kernel, SWC, NEC, SSC)
 #define BY_DEPTH(SWC) do { \
         if (src_scale) { if (depth == 8) LAUNCH(SWC, 8, true); else LAUNCH(SWC, 4, true); } \
         else { if (depth == 8) LAUNCH(SWC, 8, false); else LAUNCH(SWC, 4, false); } \
     } while (0)
-#define LAUNCH_W(NEC, SSC) spmm_packed_wave_kernel<NEC, SSC><<<grid, block, 0, s>>>( \
-        indices, xl, xr, pk, y, src_scale, dst_scale, seg_row, seg_e0, \
-        seg_e1, seg_part, part, addend, n_seg, F, n_local, \
-        pack_meta_bytes(F), pack_stride(F))
+#define LAUNCH_W(NEC, SSC) LAUNCH_K(spmm_packed_wave_kernel, NEC, SSC)
     switch (sw) {
         case 64:
             if (src_scale) { if (depth == 8) LAUNCH_W(8, true); else LAUNCH_W(4, true); }
@@ -436,4 +467,6 @@ void launch_spmm_packed(
 #undef LAUNCH_W
 #undef BY_DEPTH
 #undef LAUNCH
+#undef LAUNCH_K
+#undef LAUNCH_O
 }

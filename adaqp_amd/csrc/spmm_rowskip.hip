@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(RL_THREADS) row_live_kernel(
 // ---------------------------------------------------------------------------
 // gather
 // ---------------------------------------------------------------------------
-template <int SW, int VE, bool SS>
+template <int SW, int VE, bool SS, bool ORD>
 __global__ void __launch_bounds__(256) spmm_rowskip_kernel(
     const int32_t* __restrict__ indices,
     const float* __restrict__ xl, const float* __restrict__ xr,
@@ -114,7 +114,8 @@ __global__ void __launch_bounds__(256) spmm_rowskip_kernel(
     const int32_t* __restrict__ seg_row, const int32_t* __restrict__ seg_e0,
     const int32_t* __restrict__ seg_e1, const int32_t* __restrict__ seg_part,
     float* __restrict__ part, const float* __restrict__ addend,
-    int64_t n_seg, int64_t F, int64_t n_local) {
+    int64_t n_seg, int64_t F, int64_t n_local,
+    int chunk, int32_t* __restrict__ ticket) {
     using Raw = typename RawVec<VE * 4>::type;
     const int rows_per_block = blockDim.x / SW;
     // bijective XCD swizzle, as spmm_csr_kernel
@@ -126,8 +127,14 @@ __global__ void __launch_bounds__(256) spmm_rowskip_kernel(
     const int64_t stride = nwg * rows_per_block;
     const int sl = threadIdx.x & (SW - 1);
     const int64_t last_local = n_local - 1;              // n_local > 0
-
-    for (int64_t it = sub0; it < n_seg; it += stride) {
+    // !ORD: one pass of the static grid-stride loop; ORD: the ordered
+    // sweep, as spmm_csr_kernel (next_chunk in device_common.h)
+    const int wsub = (threadIdx.x & (WAVE - 1)) / SW;
+    for (int64_t c0 = ORD ? next_chunk(ticket, chunk) : 0; c0 < n_seg;
+         c0 = ORD ? next_chunk(ticket, chunk) : n_seg) {
+    const int64_t c1 = ORD ? min(c0 + chunk, n_seg) : n_seg;
+    for (int64_t it = ORD ? c0 + wsub : sub0; it < c1;
+         it += ORD ? WAVE / SW : stride) {
         const int64_t r = seg_row[it];
         const int64_t e0 = seg_e0[it], e1 = seg_e1[it];
         const int64_t slot = seg_part[it];     // >= 0: row split across segments
@@ -210,6 +217,7 @@ __global__ void __launch_bounds__(256) spmm_rowskip_kernel(
             }
         }
     }
+    }
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -278,23 +286,38 @@ void launch_spmm_rowskip(
     const uint8_t* live, float* y, const float* src_scale,
     const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
     const int32_t* seg_e1, const int32_t* seg_part, float* part,
-    const float* addend, int64_t n_seg, int64_t F, int64_t n_local) {
+    const float* addend, int64_t n_seg, int64_t F, int64_t n_local,
+    int order, int chunk, int32_t* ticket) {
     int ve, sw;
     spmm_rowskip_shape(F, &ve, &sw);
     const int block_threads = 256;
     const int rows_per_block = block_threads / sw;
-    int64_t blocks = (n_seg + rows_per_block - 1) / rows_per_block;
-    blocks = std::max<int64_t>(std::min<int64_t>(blocks, 16384), 1);
-    const dim3 grid(blocks), block(block_threads);
-#define LAUNCH(SWC, VEC, SSC) spmm_rowskip_kernel<SWC, VEC, SSC><<<grid, block, 0, s>>>( \
-        indices, xl, xr, live, y, src_scale, dst_scale, seg_row, seg_e0, \
-        seg_e1, seg_part, part, addend, n_seg, F, n_local)
+    const int64_t needed = (n_seg + rows_per_block - 1) / rows_per_block;
+    const int64_t blocks = std::max<int64_t>(std::min<int64_t>(needed, 16384), 1);
+    const dim3 block(block_threads);
+    // order 1: the resident blocks of the instantiation, see ordered_grid
+#define LAUNCH_O(SWC, VEC, SSC, ORDC) do { \
+        dim3 grid(blocks); \
+        if (ORDC) { \
+            grid = dim3(ordered_grid(spmm_rowskip_kernel<SWC, VEC, SSC, ORDC>, \
+                                     block_threads, needed)); \
+            TORCH_CHECK(grid.x > 0, "row-skipping spmm: occupancy query failed"); \
+        } \
+        spmm_rowskip_kernel<SWC, VEC, SSC, ORDC><<<grid, block, 0, s>>>( \
+            indices, xl, xr, live, y, src_scale, dst_scale, seg_row, seg_e0, \
+            seg_e1, seg_part, part, addend, n_seg, F, n_local, chunk, ticket); \
+    } while (0)
+#define LAUNCH(SWC, VEC, SSC) do { \
+        if (order) LAUNCH_O(SWC, VEC, SSC, true); \
+        else LAUNCH_O(SWC, VEC, SSC, false); \
+    } while (0)
 #define RUN_SPMM(SWC, VEC) do { \
         if (src_scale) LAUNCH(SWC, VEC, true); else LAUNCH(SWC, VEC, false); \
     } while (0)
     BY_SHAPE(RUN_SPMM);
 #undef RUN_SPMM
 #undef LAUNCH
+#undef LAUNCH_O
 }
 #undef BY_VE
 #undef BY_SHAPE

@@ -121,6 +121,14 @@ SEG_EDGES = int(_os.environ.get('ADAQP_SEG_EDGES', '256'))
 WAVE_INDEX = _os.environ.get('ADAQP_SPMM_WAVE_INDEX', '0') == '1'
 # row fetches in flight per lane in the packed-gather SpMM (4 or 8)
 PACKED_DEPTH = int(_os.environ.get('ADAQP_SPMM_PACKED_DEPTH', '4'))
+# how the dense per-lane, fp32 packed and row-skipping SpMM kernels hand out
+# segments: 0 = static swizzle plus grid stride, 1 = ordered sweep (a grid of
+# the resident blocks; every wavefront takes tickets of SPMM_CHUNK segments
+# from one counter, so the whole GPU walks the rows front to back once).
+# Same bits either way. ADAQP_SPMM_ORDER / ADAQP_SPMM_CHUNK, read once, here;
+# the measurement behind the defaults is profiles/spmm_order_NOTES.md.
+SPMM_ORDER = int(_os.environ.get('ADAQP_SPMM_ORDER', '1'))
+SPMM_CHUNK = int(_os.environ.get('ADAQP_SPMM_CHUNK', '4'))
 
 
 def _auto_seg(num_edges: int, num_rows: int) -> int:
@@ -460,7 +468,9 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
          packed: Union[PackedRows, 'PackedRowsBf16', None] = None,
          packed_depth: Optional[int] = None,
          out_dtype: Optional[torch.dtype] = None,
-         live: Optional[Tensor] = None) -> Tensor:
+         live: Optional[Tensor] = None,
+         order: Optional[int] = None,
+         chunk: Optional[int] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
     Columns < len(x_local) read x_local; the rest read x_remote (the
@@ -496,6 +506,10 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     read as zeros. Not combined with ``packed`` or ``out_dtype``; with a
     fusable ``QuantRemote`` the quantized-gather kernel runs and ``live`` is
     not used for that call. Ignored on the CPU.
+    ``order`` / ``chunk``: how the GPU kernel hands out segments (None =
+    SPMM_ORDER / SPMM_CHUNK): 0 the static order, 1 the ordered sweep in
+    tickets of ``chunk`` segments. Same result bit for bit. The mixed,
+    quantized, bf16 packed and wave-index kernels only have the static order.
     """
     assert live is None or (packed is None and out_dtype is None), \
         'live is not combined with packed or out_dtype'
@@ -523,6 +537,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
         else:
             assert out.is_contiguous() and out.shape[0] == num_rows
         empty = torch.empty(0, device=x_local.device)
+        order = int(SPMM_ORDER if order is None else order)
+        chunk = int(SPMM_CHUNK if chunk is None else chunk)
         if addend is not None:
             assert (addend.is_contiguous() and addend.dtype == out.dtype
                     and addend.shape == out.shape)
@@ -542,7 +558,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
                 dst_scale if dst_scale is not None else empty,
                 view.seg_row, view.seg_e0, view.seg_e1, view.seg_part,
                 view.zero_rows, view.part_ptr, view.n_part,
-                addend if addend is not None else empty, live)
+                addend if addend is not None else empty, live,
+                order, chunk)
             return out
         native().spmm_csr(indices, x_local,
                           x_remote if x_remote is not None else empty, out,
@@ -558,7 +575,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
                           int(PACKED_DEPTH if packed_depth is None
                               else packed_depth),
                           quant.payload if quant is not None else empty,
-                          quant.descriptors() if quant is not None else empty)
+                          quant.descriptors() if quant is not None else empty,
+                          order, chunk)
         return out
     x = (torch.cat([x_local, x_remote], dim=0)
          if x_remote is not None and x_remote.numel() else x_local)

@@ -23,7 +23,13 @@ addend), alternated call by call on the same view.
 ``--zero-rows 0,0.34,0.92`` times the fp32 dense kernel against ``row_live``
 plus the row-skipping kernel (the output layer's backward), once per fraction
 of all-zero rows, alternated call by call with an fp32 addend, after checking
-that the two give the same bits."""
+that the two give the same bits.
+
+``--order 0,1`` alternates the static segment order and the ordered sweep call
+by call, the sweep once per ``--chunk`` size (``--chunk 1,4,16,64``), after
+asserting that all give the same bits. Alone it times the dense kernel; with
+``--packed 1`` the packed-gather kernel at each ``--density``, with
+``--zero-rows`` the row-skipping kernel at each fraction."""
 import argparse
 import os
 import statistics
@@ -80,6 +86,13 @@ def main():
                    help='fractions of all-zero rows, e.g. "0,0.34,0.92": fp32 '
                         'dense kernel against row_live plus the row-skipping '
                         'kernel, alternated call by call')
+    p.add_argument('--order', type=str, default=None,
+                   help='"0,1": static segment order and ordered sweep '
+                        'alternated call by call; combines with --packed 1 '
+                        'and --zero-rows')
+    p.add_argument('--chunk', type=str, default='4',
+                   help='segments per ticket of the ordered sweep, e.g. '
+                        '"1,4,16,64"')
     args = p.parse_args()
     assert torch.cuda.is_available()
     from adaqp_amd.ops.kernels import SpmmView, spmm, native
@@ -95,6 +108,10 @@ def main():
     gather_bytes = E * (args.F * x.element_size() + 12)
     head = (f'rows={args.rows} E={E} F={args.F} {args.dtype} '
             f'cb={args.col_block}')
+
+    if args.order is not None:
+        order_bench(args, view, x, src, dst, head)
+        return
 
     if args.packed is not None:
         packed_bench(args, view, x, src, dst, E, head)
@@ -161,6 +178,63 @@ def _timed(fn):
 
 def _fmt(t):
     return f'{statistics.median(t):.3f} ms ({min(t):.3f}..{max(t):.3f})'
+
+
+def order_bench(args, view, x, src, dst, head):
+    """Static order against the ordered sweep at each chunk size, on the
+    dense, the packed-gather (--packed 1) or the row-skipping (--zero-rows)
+    kernel."""
+    from adaqp_amd.ops.kernels import pack_rows, row_live, spmm
+    orders = [int(o) for o in args.order.split(',')]
+    variants = ([(0, 4)] if 0 in orders else []) + (
+        [(1, int(c)) for c in args.chunk.split(',')] if 1 in orders else [])
+    E = int(view.indices.numel())
+    gen = torch.Generator(device=x.device).manual_seed(7)
+    if args.packed is not None:
+        assert x.dtype == torch.float32 and '1' in args.packed.split(',')
+        cases = [('density', float(d)) for d in args.density.split(',')]
+    elif args.zero_rows is not None:
+        assert x.dtype == torch.float32
+        cases = [('zero rows', float(f)) for f in args.zero_rows.split(',')]
+    else:
+        cases = [('dense', None)]
+    for kind, val in cases:
+        kw, xc = {}, x
+        if kind == 'density':
+            xc = (x * (torch.rand(x.shape, device=x.device, generator=gen)
+                       < val)).contiguous()
+            kw = {'packed': pack_rows(xc)}
+            assert kw['packed'] is not None
+        elif kind == 'zero rows':
+            keep = torch.rand(x.shape[0], device=x.device, generator=gen) >= val
+            xc = (x * keep[:, None]).contiguous()
+            kw = {'live': row_live(xc),
+                  'addend': torch.randn(args.rows, args.F, device=x.device)}
+        outs = {}
+        for _ in range(3):
+            for v in variants:
+                outs[v] = spmm(view, xc, None, src, dst, order=v[0],
+                               chunk=v[1], **kw)
+        torch.cuda.synchronize()
+        for v in variants[1:]:
+            assert torch.equal(outs[variants[0]], outs[v]), \
+                f'order/chunk {v} differs from {variants[0]}'
+        print(f'{head} {kind}{"" if val is None else " " + str(val)}: outputs '
+              f'of {len(variants)} traversals bit-identical: True')
+        del outs
+        times = {v: [] for v in variants}
+        for _ in range(args.iters):
+            for v in variants:
+                t, _ = _timed(lambda: spmm(view, xc, None, src, dst,
+                                           order=v[0], chunk=v[1], **kw))
+                times[v].append(t)
+        for v in variants:
+            name = 'static order' if v[0] == 0 else f'ordered, chunk {v[1]}'
+            med = statistics.median(times[v])
+            print(f'  {name}: {_fmt(times[v])}, {E / (med * 1e-3) / 1e9:.2f} '
+                  f'G edges/s')
+        sys.stdout.flush()
+        del xc, kw
 
 
 def packed_bench(args, view, x, src, dst, E, head):
