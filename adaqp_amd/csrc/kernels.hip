@@ -659,6 +659,17 @@ void launch_spmm_rowskip(
     const float* addend, int64_t n_seg, int64_t F, int64_t n_local,
     int order, int chunk, int32_t* ticket);
 
+// spmm_compact.hip
+torch::Tensor row_live_bf16(torch::Tensor x);
+void spmm_compact_shape(bool bf16, int64_t F, int* ve, int* sw);
+void launch_spmm_compact(
+    hipStream_t s, bool bf16, const int32_t* indices, const void* xl,
+    const void* xr, const uint8_t* live, void* y, const float* src_scale,
+    const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
+    const int32_t* seg_e1, const int32_t* seg_part, float* part,
+    const void* addend, int64_t n_seg, int64_t F, int64_t n_local,
+    int order, int chunk, int32_t* ticket);
+
 static inline hipStream_t cur_stream() {
     return at::cuda::getCurrentHIPStream().stream();
 }
@@ -1163,6 +1174,126 @@ void spmm_csr_rowskip(torch::Tensor indices, torch::Tensor xl,
     }
 }
 
+// Edge-compacting row-skipping spmm_csr (spmm_compact.hip), fp32 or bf16:
+// `live` is row_live(xl) / row_live_bf16(xl); a sub-wavefront finds the live
+// edges of a segment with one ballot per chunk of its width and fetches only
+// their rows. Same bits as spmm_csr on the same operands.
+void spmm_csr_compact(torch::Tensor indices, torch::Tensor xl,
+                      torch::Tensor xr, torch::Tensor y,
+                      torch::Tensor src_scale, torch::Tensor dst_scale,
+                      torch::Tensor seg_row, torch::Tensor seg_e0,
+                      torch::Tensor seg_e1, torch::Tensor seg_part,
+                      torch::Tensor zero_rows, torch::Tensor part_ptr,
+                      int64_t n_part, torch::Tensor addend,
+                      torch::Tensor live, int64_t order, int64_t chunk) {
+    CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
+    const auto dt = xl.scalar_type();
+    const bool bf16 = dt == torch::kBFloat16;
+    TORCH_CHECK(xl.dim() == 2 && (bf16 || dt == torch::kFloat32) &&
+                y.dim() == 2 && y.scalar_type() == dt,
+                "compacting spmm expects fp32 or bf16 [N, F] rows and a y of "
+                "the same dtype");
+    const int64_t F = xl.size(1);
+    const int64_t n_local = xl.size(0);
+    const int64_t n_seg = seg_row.numel();
+    TORCH_CHECK(F > 0 && y.size(1) == F && n_local > 0 && (!bf16 || F % 2 == 0),
+                "compacting spmm needs F > 0 (even for bf16), the same in x "
+                "and y, and at least one local row");
+    CHECK_DEV(live); CHECK_CONTIG(live);
+    TORCH_CHECK(live.scalar_type() == torch::kUInt8 && live.dim() == 1 &&
+                live.numel() == n_local,
+                "live must be row_live(xl): uint8 [n_local]");
+    int ve, sw;
+    spmm_compact_shape(bf16, F, &ve, &sw);
+    auto aligned = [&](const void* p) {
+        return reinterpret_cast<uintptr_t>(p) % (ve * (bf16 ? 2 : 4)) == 0;
+    };
+    const void* xr_ptr = nullptr;
+    int64_t n_remote = 0;
+    if (xr.numel()) {
+        CHECK_DEV(xr); CHECK_CONTIG(xr);
+        TORCH_CHECK(xr.dim() == 2 && xr.size(1) == F && xr.scalar_type() == dt,
+                    "compacting spmm: the remote block must be [R, F] of x's "
+                    "dtype");
+        xr_ptr = xr.data_ptr();
+        n_remote = xr.size(0);
+    }
+    // the kernel does its column arithmetic in 32 bits
+    TORCH_CHECK(F < (1ll << 31) && n_local + n_remote < (1ll << 31),
+                "compacting spmm: F and the column count must fit 31 bits");
+    const void* ad_ptr = nullptr;
+    if (addend.dim() == 2) {        // a 1-D empty tensor means "none"
+        CHECK_DEV(addend); CHECK_CONTIG(addend);
+        TORCH_CHECK(addend.size(0) == y.size(0) && addend.size(1) == F &&
+                    addend.scalar_type() == dt,
+                    "compacting spmm: addend must be [nrows, F] of y's dtype");
+        ad_ptr = addend.numel() ? addend.data_ptr() : nullptr;
+    }
+    TORCH_CHECK(aligned(xl.data_ptr()) && aligned(xr_ptr) &&
+                aligned(y.data_ptr()) && aligned(ad_ptr),
+                "compacting spmm: operands must be aligned to the vector "
+                "load width");
+    for (const torch::Tensor* t : {&indices, &seg_row, &seg_e0, &seg_e1,
+                                   &seg_part, &zero_rows, &part_ptr})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous(),
+                    "compacting spmm: the view's arrays must be on the GPU");
+    TORCH_CHECK((!src_scale.numel() || src_scale.is_cuda()) &&
+                (!dst_scale.numel() || dst_scale.is_cuda()),
+                "compacting spmm: scale vectors must be on the GPU");
+    TORCH_CHECK(indices.scalar_type() == torch::kInt32 &&
+                seg_row.scalar_type() == torch::kInt32 &&
+                seg_e0.scalar_type() == torch::kInt32 &&
+                seg_e1.scalar_type() == torch::kInt32 &&
+                seg_part.scalar_type() == torch::kInt32 &&
+                seg_e0.numel() == n_seg && seg_e1.numel() == n_seg &&
+                seg_part.numel() == n_seg &&
+                zero_rows.scalar_type() == torch::kInt32 &&
+                part_ptr.scalar_type() == torch::kInt32 &&
+                part_ptr.numel() == zero_rows.numel() + 1,
+                "compacting spmm expects the int32 arrays SpmmView builds");
+    TORCH_CHECK(n_part >= 0 && n_part <= n_seg, "bad partial slot count");
+    TORCH_CHECK(!src_scale.numel() ||
+                (src_scale.scalar_type() == torch::kFloat32 &&
+                 src_scale.numel() >= n_local + n_remote),
+                "compacting spmm: src_scale must be fp32 and cover every "
+                "column");
+    TORCH_CHECK(!dst_scale.numel() ||
+                (dst_scale.scalar_type() == torch::kFloat32 &&
+                 dst_scale.numel() == y.size(0)),
+                "compacting spmm: dst_scale must be fp32 [nrows]");
+    auto s = cur_stream();
+    torch::Tensor part = torch::empty(
+        {n_part, F}, y.options().dtype(torch::kFloat32));
+    check_order(order, chunk);
+    torch::Tensor ticket;
+    if (n_seg && order) ticket = new_ticket(y, s);
+    if (n_seg)
+        launch_spmm_compact(
+            s, bf16, indices.data_ptr<int32_t>(), xl.data_ptr(), xr_ptr,
+            live.data_ptr<uint8_t>(), y.data_ptr(),
+            src_scale.numel() ? src_scale.data_ptr<float>() : nullptr,
+            dst_scale.numel() ? dst_scale.data_ptr<float>() : nullptr,
+            seg_row.data_ptr<int32_t>(), seg_e0.data_ptr<int32_t>(),
+            seg_e1.data_ptr<int32_t>(), seg_part.data_ptr<int32_t>(),
+            part.data_ptr<float>(), ad_ptr, n_seg, F, n_local,
+            (int)order, (int)chunk,
+            order ? ticket.data_ptr<int32_t>() : nullptr);
+    if (zero_rows.numel()) {
+        const dim3 zb(256), zg((zero_rows.numel() + 3) / 4);
+        if (bf16)
+            combine_parts_kernel<ushort><<<zg, zb, 0, s>>>(
+                reinterpret_cast<ushort*>(y.data_ptr()),
+                part.data_ptr<float>(), zero_rows.data_ptr<int32_t>(),
+                part_ptr.data_ptr<int32_t>(),
+                reinterpret_cast<const ushort*>(ad_ptr), zero_rows.numel(), F);
+        else
+            combine_parts_kernel<float><<<zg, zb, 0, s>>>(
+                y.data_ptr<float>(), part.data_ptr<float>(),
+                zero_rows.data_ptr<int32_t>(), part_ptr.data_ptr<int32_t>(),
+                reinterpret_cast<const float*>(ad_ptr), zero_rows.numel(), F);
+    }
+}
+
 
 // norm_act.hip
 void norm_act_fwd(torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
@@ -1257,6 +1388,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("spmm_csr_rowskip", &spmm_csr_rowskip,
           "fp32 spmm_csr that does not fetch the local rows row_live marks "
           "as all zero (CDNA4)",
+          pybind11::arg("indices"), pybind11::arg("xl"), pybind11::arg("xr"),
+          pybind11::arg("y"), pybind11::arg("src_scale"),
+          pybind11::arg("dst_scale"), pybind11::arg("seg_row"),
+          pybind11::arg("seg_e0"), pybind11::arg("seg_e1"),
+          pybind11::arg("seg_part"), pybind11::arg("zero_rows"),
+          pybind11::arg("part_ptr"), pybind11::arg("n_part"),
+          pybind11::arg("addend"), pybind11::arg("live"),
+          pybind11::arg("order") = 0, pybind11::arg("chunk") = 4);
+    m.def("row_live_bf16", &row_live_bf16,
+          "uint8 [N]: 1 where a row of the bf16 [N, F] tensor (even F) holds "
+          "a non-zero magnitude (CDNA4)");
+    m.def("spmm_csr_compact", &spmm_csr_compact,
+          "fp32 / bf16 spmm_csr that finds a segment's live edges with one "
+          "ballot per chunk and fetches only their rows (CDNA4)",
           pybind11::arg("indices"), pybind11::arg("xl"), pybind11::arg("xr"),
           pybind11::arg("y"), pybind11::arg("src_scale"),
           pybind11::arg("dst_scale"), pybind11::arg("seg_row"),

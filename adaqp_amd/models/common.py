@@ -36,6 +36,10 @@ SPMM_PACKED_BF16_DEFAULT = '0'
 # either way; profiles/spmm_rowskip_NOTES.md has the measurement behind the
 # default.
 BWD_SKIP_ZERO_DEFAULT = '1'
+# ADAQP_BWD_SKIP_ZERO_BF16=0/1: the same for a bf16 engine, through the
+# edge-compacting kernel (csrc/spmm_compact.hip). Same bits either way; off
+# until profiles/spmm_compact_NOTES.md says otherwise.
+BWD_SKIP_ZERO_BF16_DEFAULT = '0'
 
 
 def spmm_packed_bf16_on() -> bool:
@@ -246,7 +250,9 @@ class _SageMeanFn(torch.autograd.Function):
     ADAQP_BWD_SKIP_ZERO on an fp32 GPU engine marks them in one pass
     (``row_live``) and the backward SpMM does not fetch them: same bits,
     fewer bytes. The marks come from the data, so a wrong hint only costs
-    the pass. Not combined with the bf16 gather, which wins."""
+    the pass. Not combined with the bf16 gather, which wins. A bf16 GPU
+    engine does the same with ADAQP_BWD_SKIP_ZERO_BF16 on (even F), through
+    the edge-compacting kernel of csrc/spmm_compact.hip."""
 
     @staticmethod
     def forward(ctx, x: Tensor, w1: Tensor, w2: Tensor, b1: Tensor,
@@ -278,7 +284,8 @@ class _SageMeanFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g: Tensor):
         from ..ops.dist_agg import propagate, next_bwd_gather_seed
-        from ..ops.kernels import resolve_bwd_skip_zero, row_live
+        from ..ops.kernels import (resolve_bwd_skip_zero,
+                                   resolve_bwd_skip_zero_bf16, row_live)
         from ..helpers import PropagationMode
         xs, h, w1, w2 = ctx.saved_tensors
         engine = ctx.engine
@@ -300,6 +307,17 @@ class _SageMeanFn(torch.autograd.Function):
                     and resolve_bwd_skip_zero(
                         getattr(engine, 'bwd_skip_zero', None),
                         BWD_SKIP_ZERO_DEFAULT)):
+                kw = {'live': row_live(gh)}
+                engine.bwd_skip_hits = getattr(engine, 'bwd_skip_hits', 0) + 1
+            # ADAQP_BWD_SKIP_ZERO_BF16 (output layer, bf16 engines on the
+            # GPU): the same through the edge-compacting kernel
+            elif (ctx.sparse_grad and seed is None and gh.is_cuda
+                    and engine.compute_dtype == torch.bfloat16
+                    and gh.dtype == torch.bfloat16 and gh.shape[0] > 0
+                    and gh.shape[1] > 0 and gh.shape[1] % 2 == 0
+                    and resolve_bwd_skip_zero_bf16(
+                        getattr(engine, 'bwd_skip_zero_bf16', None),
+                        BWD_SKIP_ZERO_BF16_DEFAULT)):
                 kw = {'live': row_live(gh)}
                 engine.bwd_skip_hits = getattr(engine, 'bwd_skip_hits', 0) + 1
             if gx_self.dtype == gh.dtype == ctx.in_dtype:

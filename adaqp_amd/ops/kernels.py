@@ -129,6 +129,13 @@ PACKED_DEPTH = int(_os.environ.get('ADAQP_SPMM_PACKED_DEPTH', '4'))
 # the measurement behind the defaults is profiles/spmm_order_NOTES.md.
 SPMM_ORDER = int(_os.environ.get('ADAQP_SPMM_ORDER', '1'))
 SPMM_CHUNK = int(_os.environ.get('ADAQP_SPMM_CHUNK', '4'))
+# which kernel an fp32 spmm(..., live=) runs: False = spmm_rowskip_kernel
+# (walks every edge, predicates the row fetch), True = spmm_compact_kernel
+# (one ballot per chunk of edges, fetch slots spent on live edges only). A
+# bf16 call with live= always runs the compacting kernel, the only one it
+# has. Same bits either way. ADAQP_SPMM_COMPACT=1 turns it on (read once,
+# here); profiles/spmm_compact_NOTES.md has the measurement.
+SPMM_COMPACT = _os.environ.get('ADAQP_SPMM_COMPACT', '0') == '1'
 
 
 def _auto_seg(num_edges: int, num_rows: int) -> int:
@@ -377,14 +384,29 @@ def resolve_bwd_skip_zero(flag: Optional[bool], default: str) -> bool:
     return bool(flag)
 
 
+def resolve_bwd_skip_zero_bf16(flag: Optional[bool], default: str) -> bool:
+    """:func:`resolve_bwd_skip_zero` for bf16 engines: ``None`` -> env
+    ``ADAQP_BWD_SKIP_ZERO_BF16`` (``default`` when unset) is '1'; an explicit
+    bool wins. (``GraphEngine.bwd_skip_zero_bf16`` is the flag.)"""
+    if flag is None:
+        return _os.environ.get('ADAQP_BWD_SKIP_ZERO_BF16', default) == '1'
+    return bool(flag)
+
+
 def row_live(x: Tensor) -> Tensor:
-    """uint8 [N] for an fp32 [N, F] tensor: 1 where the row holds an element
-    of non-zero magnitude, by bit pattern (``bits & 0x7fffffff != 0``), so
-    denormals, NaN and Inf count and -0.0 does not. GPU: one pass of the
-    native kernel (csrc/spmm_rowskip.hip); CPU: the same definition in torch
-    integer ops. The ``live=`` operand of :func:`spmm`."""
-    assert x.dtype == torch.float32 and x.dim() == 2
+    """uint8 [N] for an fp32 or bf16 [N, F] tensor (bf16: even F): 1 where
+    the row holds an element of non-zero magnitude, by bit pattern
+    (``bits & 0x7fffffff != 0``, bf16 ``bits & 0x7fff != 0``), so denormals,
+    NaN and Inf count and -0.0 does not. GPU: one pass of the native kernel
+    (csrc/spmm_rowskip.hip, bf16 csrc/spmm_compact.hip); CPU: the same
+    definition in torch integer ops. The ``live=`` operand of :func:`spmm`."""
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2
     x = x.contiguous()
+    if x.dtype == torch.bfloat16:
+        assert x.shape[1] % 2 == 0, 'row_live on bf16 needs an even F'
+        if x.is_cuda:
+            return native().row_live_bf16(x)
+        return ((x.view(torch.int16) & 0x7FFF) != 0).any(dim=1).to(torch.uint8)
     if x.is_cuda:
         return native().row_live(x)
     return ((x.view(torch.int32) & 0x7FFFFFFF) != 0).any(dim=1).to(torch.uint8)
@@ -470,7 +492,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
          out_dtype: Optional[torch.dtype] = None,
          live: Optional[Tensor] = None,
          order: Optional[int] = None,
-         chunk: Optional[int] = None) -> Tensor:
+         chunk: Optional[int] = None,
+         compact: Optional[bool] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
     Columns < len(x_local) read x_local; the rest read x_remote (the
@@ -500,12 +523,19 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     which is dequantized into a bf16 block), ``out`` and ``addend`` are
     fp32 and ``packed`` must be None. The rows are only gathered in bf16;
     the result equals ``spmm`` on the widened operands bit for bit.
-    ``live``: ``row_live(x_local)`` (GPU fp32 only); local rows it marks as
-    all zero are not fetched (csrc/spmm_rowskip.hip), same result bit for
-    bit. A 0 for a row that holds a non-zero is a misuse: that row is then
-    read as zeros. Not combined with ``packed`` or ``out_dtype``; with a
-    fusable ``QuantRemote`` the quantized-gather kernel runs and ``live`` is
-    not used for that call. Ignored on the CPU.
+    ``live``: ``row_live(x_local)`` (GPU, fp32 or bf16 with even F); local
+    rows it marks as all zero are not fetched, same result bit for bit. A 0
+    for a row that holds a non-zero is a misuse: that row is then read as
+    zeros. Not combined with ``packed`` or ``out_dtype``; with a fusable
+    ``QuantRemote`` the quantized-gather kernel runs and ``live`` is not used
+    for that call. Ignored on the CPU.
+    ``compact``: which row-skipping kernel an fp32 call with ``live`` runs
+    (None = SPMM_COMPACT): False the edge-walking one
+    (csrc/spmm_rowskip.hip), True the edge-compacting one
+    (csrc/spmm_compact.hip), which finds a segment's live edges with one
+    ballot per chunk and spends its row fetches on them alone. A bf16 call
+    with ``live`` always runs the compacting kernel. Same result bit for bit.
+    Without ``live``, and on the CPU, it is ignored.
     ``order`` / ``chunk``: how the GPU kernel hands out segments (None =
     SPMM_ORDER / SPMM_CHUNK): 0 the static order, 1 the ordered sweep in
     tickets of ``chunk`` segments. Same result bit for bit. The mixed,
@@ -546,12 +576,17 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
             assert packed.matches(x_local), \
                 'packed operand was not made from x_local'
         if live is not None and x_local.shape[0] > 0:
-            assert x_local.dtype == torch.float32, \
-                'the row-skipping spmm is fp32 only'
+            bf16 = x_local.dtype == torch.bfloat16
+            assert bf16 or x_local.dtype == torch.float32, \
+                'the row-skipping spmm is fp32 or bf16'
             assert (live.dtype == torch.uint8
                     and live.shape == (x_local.shape[0],)), \
                 'live operand was not made from x_local'
-            native().spmm_csr_rowskip(
+            use_compact = bf16 or bool(SPMM_COMPACT if compact is None
+                                       else compact)
+            run = (native().spmm_csr_compact if use_compact
+                   else native().spmm_csr_rowskip)
+            run(
                 indices, x_local,
                 x_remote if x_remote is not None else empty, out,
                 src_scale if src_scale is not None else empty,

@@ -65,6 +65,10 @@ class GraphEngine:
         # counts the backward SpMMs that took the row-skipping path.
         self.bwd_skip_zero: Optional[bool] = None
         self.bwd_skip_hits = 0
+        # the same for a bf16 engine. None: env ADAQP_BWD_SKIP_ZERO_BF16, else
+        # the default in models/common.py (off); a bool wins. Its backward
+        # SpMMs are counted in bwd_skip_hits too.
+        self.bwd_skip_zero_bf16: Optional[bool] = None
         self.timer = Timer(enabled=False, cuda=self.device.type == 'cuda',
                            mode='events')
         self.is_tracing = False

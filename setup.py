@@ -28,6 +28,7 @@ setup(
                      'adaqp_amd/csrc/spmm_quant.hip',
                      'adaqp_amd/csrc/spmm_mixed.hip',
                      'adaqp_amd/csrc/spmm_rowskip.hip',
+                     'adaqp_amd/csrc/spmm_compact.hip',
                      'adaqp_amd/csrc/masked_loss.hip'],
             extra_compile_args={'cxx': ['-O3'],
                                 'nvcc': ['-O3', '--offload-arch=gfx950']},

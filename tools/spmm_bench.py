@@ -20,16 +20,20 @@ row fetches in flight.
 of the fp32 backward (``round_rows_bf16`` plus the mixed SpMM, with an fp32
 addend), alternated call by call on the same view.
 
-``--zero-rows 0,0.34,0.92`` times the fp32 dense kernel against ``row_live``
-plus the row-skipping kernel (the output layer's backward), once per fraction
-of all-zero rows, alternated call by call with an fp32 addend, after checking
-that the two give the same bits.
+``--zero-rows 0,0.34,0.92`` times the dense kernel against ``row_live`` plus
+the row-skipping kernel (the output layer's backward), once per fraction of
+all-zero rows, alternated call by call with an addend, after asserting that
+all give the same bits. ``--compact 0,1`` picks the row-skipping kernels: 0 the
+edge-walking one (fp32 only), 1 the edge-compacting one (fp32 and
+``--dtype bf16``, which has no other); with ``--order 0,1`` every kernel,
+the dense one included, runs once per segment order.
 
 ``--order 0,1`` alternates the static segment order and the ordered sweep call
 by call, the sweep once per ``--chunk`` size (``--chunk 1,4,16,64``), after
 asserting that all give the same bits. Alone it times the dense kernel; with
 ``--packed 1`` the packed-gather kernel at each ``--density``, with
-``--zero-rows`` the row-skipping kernel at each fraction."""
+``--zero-rows`` the row-skipping kernel at each fraction (with ``--compact``
+as well: see above)."""
 import argparse
 import os
 import statistics
@@ -86,6 +90,10 @@ def main():
                    help='fractions of all-zero rows, e.g. "0,0.34,0.92": fp32 '
                         'dense kernel against row_live plus the row-skipping '
                         'kernel, alternated call by call')
+    p.add_argument('--compact', type=str, default=None,
+                   help='with --zero-rows: "0,1" the edge-walking (fp32) '
+                        'and the edge-compacting row-skipping kernel, '
+                        'alternated call by call with the dense one')
     p.add_argument('--order', type=str, default=None,
                    help='"0,1": static segment order and ordered sweep '
                         'alternated call by call; combines with --packed 1 '
@@ -108,6 +116,11 @@ def main():
     gather_bytes = E * (args.F * x.element_size() + 12)
     head = (f'rows={args.rows} E={E} F={args.F} {args.dtype} '
             f'cb={args.col_block}')
+
+    if args.zero_rows is not None and (args.compact is not None
+                                       or x.dtype == torch.bfloat16):
+        zero_rows_bench(args, view, x, src, dst, head)
+        return
 
     if args.order is not None:
         order_bench(args, view, x, src, dst, head)
@@ -332,50 +345,72 @@ def gather_bf16_bench(args, view, x, src, dst, head):
 
 
 def zero_rows_bench(args, view, x, src, dst, head):
-    """fp32 dense SpMM against row_live + the row-skipping SpMM on the same
-    view, with an fp32 addend as the SAGE backward has one; rows are zeroed
-    i.i.d. with each given probability."""
+    """Dense SpMM against row_live + the row-skipping SpMMs (--compact: 0 the
+    edge-walking kernel, 1 the edge-compacting one) on the same view, with an
+    addend as the SAGE backward has one; rows are zeroed i.i.d. with each
+    given probability. With --order every kernel runs once per order."""
     from adaqp_amd.ops.kernels import row_live, spmm
-    assert x.dtype == torch.float32
-    addend = torch.randn(args.rows, args.F, device=x.device)
+    bf16 = x.dtype == torch.bfloat16
+    compacts = ([1] if bf16 else
+                [int(c) for c in (args.compact or '0').split(',')])
+    assert not bf16 or args.F % 2 == 0
+    orders = ([None] if args.order is None
+              else [int(o) for o in args.order.split(',')])
+    chunk = int(args.chunk.split(',')[0])
+    # (name, order, compact); compact None = the dense kernel
+    variants = [(f'{k}{"" if o is None else f", order {o}"}', o, c)
+                for k, c in [('dense', None)]
+                + [(('compacting' if c else 'edge-walking'), c)
+                   for c in compacts]
+                for o in orders]
+    addend = torch.randn(args.rows, args.F, device=x.device).to(x.dtype)
     gen = torch.Generator(device=x.device).manual_seed(11)
     E = int(view.indices.numel())
+    bits = torch.int16 if bf16 else torch.int32
     for frac in [float(f) for f in args.zero_rows.split(',')]:
         keep = torch.rand(x.shape[0], device=x.device, generator=gen) >= frac
         xz = (x * keep[:, None]).contiguous()
 
-        def dense():
-            return spmm(view, xz, None, src, dst, addend=addend)
-
         def mark():
             return row_live(xz)
 
-        def skip(live):
-            return spmm(view, xz, None, src, dst, addend=addend, live=live)
+        def run(v, live):
+            kw = {} if v[1] is None else {'order': v[1], 'chunk': chunk}
+            if v[2] is not None:
+                kw.update(live=live, compact=bool(v[2]))
+            return spmm(view, xz, None, src, dst, addend=addend, **kw)
 
+        outs = {}
         for _ in range(3):
-            yd, live = dense(), mark()
-            ys = skip(live)
+            live = mark()
+            for v in variants:
+                outs[v] = run(v, live)
         torch.cuda.synchronize()
-        same = torch.equal(ys.view(torch.int32), yd.view(torch.int32))
+        for v in variants[1:]:
+            assert torch.equal(outs[variants[0]].view(bits),
+                               outs[v].view(bits)), \
+                f'{v[0]} differs from {variants[0][0]}'
         dead = 1.0 - float(live.float().mean())
         print(f'{head} zero rows {frac} (marked dead {dead:.3f}): outputs of '
-              f'dense and row-skipping bit-identical: {same}')
-        td, tl, ts = [], [], []
+              f'{len(variants)} variants bit-identical: True')
+        del outs
+        tl, times = [], {v: [] for v in variants}
         for _ in range(args.iters):
-            td.append(_timed(dense)[0])
             t, live = _timed(mark)
             tl.append(t)
-            ts.append(_timed(lambda: skip(live))[0])
-        print(f'  fp32 dense:   {_fmt(td)}, apparent gather '
-              f'{E * (args.F * 4 + 12) / (statistics.median(td) * 1e-3) / 1e12:.2f} TB/s')
-        print(f'  row_live:     {_fmt(tl)}, '
-              f'{xz.numel() * 4 / (statistics.median(tl) * 1e-3) / 1e12:.2f} TB/s read')
-        print(f'  row-skipping: {_fmt(ts)}')
-        print(f'  row_live + row-skipping, sum of medians: '
-              f'{statistics.median(tl) + statistics.median(ts):.3f} ms')
+            for v in variants:
+                times[v].append(_timed(lambda: run(v, live))[0])
+        print(f'  row_live: {_fmt(tl)}, '
+              f'{xz.numel() * xz.element_size() / (statistics.median(tl) * 1e-3) / 1e12:.2f}'
+              f' TB/s read')
+        for v in variants:
+            med = statistics.median(times[v])
+            print(f'  {v[0]}: {_fmt(times[v])}, '
+                  f'{E / (med * 1e-3) / 1e9:.2f} G edges/s'
+                  + ('' if v[2] is None else
+                     f'; with row_live {med + statistics.median(tl):.3f} ms'))
         sys.stdout.flush()
-        del xz, keep, yd, ys, live
+        del xz, keep, live
 
 
 if __name__ == '__main__':
