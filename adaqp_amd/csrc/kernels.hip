@@ -647,6 +647,13 @@ void launch_spmm_bf16in(
     const int32_t* seg_row, const int32_t* seg_e0, const int32_t* seg_e1,
     const int32_t* seg_part, float* part, const float* addend,
     int64_t n_seg, int64_t F, int64_t n_local);
+// spmm_quant_bf16.hip
+void launch_spmm_quant_bf16(
+    hipStream_t s, bool out_f32, const int32_t* indices, const ushort* xl,
+    torch::Tensor payload, torch::Tensor desc, void* y, const float* src_scale,
+    const float* dst_scale, const int32_t* seg_row, const int32_t* seg_e0,
+    const int32_t* seg_e1, const int32_t* seg_part, float* part,
+    const void* addend, int64_t n_seg, int64_t F, int64_t n_local);
 
 // spmm_rowskip.hip
 torch::Tensor row_live(torch::Tensor x);
@@ -1068,6 +1075,113 @@ void spmm_csr_bf16in(torch::Tensor indices, torch::Tensor xl,
     }
 }
 
+// spmm_csr / spmm_csr_bf16in with the remote block left in wire form
+// (spmm_quant_bf16.hip): xl is bf16, remote columns are gathered from the
+// quantized payload through quant_row_desc's block, y (and addend) is bf16 or
+// fp32. Same bits as spmm_csr (bf16 y) or spmm_csr_bf16in (fp32 y) on the
+// payload unpacked into a bf16 block.
+void spmm_csr_quant_bf16(torch::Tensor indices, torch::Tensor xl,
+                         torch::Tensor q_payload, torch::Tensor q_desc,
+                         torch::Tensor y, torch::Tensor src_scale,
+                         torch::Tensor dst_scale, torch::Tensor seg_row,
+                         torch::Tensor seg_e0, torch::Tensor seg_e1,
+                         torch::Tensor seg_part, torch::Tensor zero_rows,
+                         torch::Tensor part_ptr, int64_t n_part,
+                         torch::Tensor addend) {
+    CHECK_DEV(xl); CHECK_CONTIG(xl); CHECK_DEV(y); CHECK_CONTIG(y);
+    const bool out_f32 = y.scalar_type() == torch::kFloat32;
+    TORCH_CHECK(xl.dim() == 2 && xl.scalar_type() == torch::kBFloat16 &&
+                y.dim() == 2 &&
+                (out_f32 || y.scalar_type() == torch::kBFloat16),
+                "quantized bf16 spmm expects bf16 [N, F] rows and a bf16 or "
+                "fp32 [nrows, F] y");
+    const int64_t F = xl.size(1);
+    const int64_t n_local = xl.size(0);
+    const int64_t n_seg = seg_row.numel();
+    TORCH_CHECK(F > 0 && F % 2 == 0 && y.size(1) == F,
+                "quantized bf16 spmm needs an even feature dim, the same in "
+                "x and y");
+    int ve, sw;
+    spmm_bf16in_shape(F, &ve, &sw);
+    // a lane's ve bf16 values are one 2 * ve-byte load; its results leave as
+    // one 2 * ve-byte store (bf16) or 16-byte (ve = 2: 8-byte) stores (fp32)
+    const uintptr_t in_al = 2 * ve;
+    const uintptr_t out_al = !out_f32 ? 2 * ve : ve == 2 ? 8 : 16;
+    auto aligned = [](const void* p, uintptr_t a) {
+        return reinterpret_cast<uintptr_t>(p) % a == 0;
+    };
+    const void* ad_ptr = nullptr;
+    if (addend.dim() == 2) {        // a 1-D empty tensor means "none"
+        CHECK_DEV(addend); CHECK_CONTIG(addend);
+        TORCH_CHECK(addend.size(0) == y.size(0) && addend.size(1) == F &&
+                    addend.scalar_type() == y.scalar_type(),
+                    "quantized bf16 spmm: addend must be [nrows, F] of y's "
+                    "dtype");
+        ad_ptr = addend.numel() ? addend.data_ptr() : nullptr;
+    }
+    TORCH_CHECK(aligned(xl.data_ptr(), in_al) &&
+                aligned(y.data_ptr(), out_al) && aligned(ad_ptr, out_al),
+                "quantized bf16 spmm: operands must be aligned to the vector "
+                "widths");
+    for (const torch::Tensor* t : {&indices, &seg_row, &seg_e0, &seg_e1,
+                                   &seg_part, &zero_rows, &part_ptr})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous(),
+                    "quantized bf16 spmm: the view's arrays must be on the GPU");
+    TORCH_CHECK((!src_scale.numel() || src_scale.is_cuda()) &&
+                (!dst_scale.numel() || dst_scale.is_cuda()),
+                "quantized bf16 spmm: scale vectors must be on the GPU");
+    TORCH_CHECK(indices.scalar_type() == torch::kInt32 &&
+                seg_row.scalar_type() == torch::kInt32 &&
+                seg_e0.scalar_type() == torch::kInt32 &&
+                seg_e1.scalar_type() == torch::kInt32 &&
+                seg_part.scalar_type() == torch::kInt32 &&
+                seg_e0.numel() == n_seg && seg_e1.numel() == n_seg &&
+                seg_part.numel() == n_seg &&
+                zero_rows.scalar_type() == torch::kInt32 &&
+                part_ptr.scalar_type() == torch::kInt32 &&
+                part_ptr.numel() == zero_rows.numel() + 1,
+                "quantized bf16 spmm expects the int32 arrays SpmmView builds");
+    TORCH_CHECK(n_part >= 0 && n_part <= n_seg, "bad partial slot count");
+    TORCH_CHECK(q_desc.dim() == 2, "quantized bf16 spmm expects an [R, 4] "
+                                   "descriptor block");
+    TORCH_CHECK(!src_scale.numel() ||
+                (src_scale.scalar_type() == torch::kFloat32 &&
+                 src_scale.numel() >= n_local + q_desc.size(0)),
+                "quantized bf16 spmm: src_scale must be fp32 and cover every "
+                "column");
+    TORCH_CHECK(!dst_scale.numel() ||
+                (dst_scale.scalar_type() == torch::kFloat32 &&
+                 dst_scale.numel() == y.size(0)),
+                "quantized bf16 spmm: dst_scale must be fp32 [nrows]");
+    auto s = cur_stream();
+    torch::Tensor part = torch::empty(
+        {n_part, F}, y.options().dtype(torch::kFloat32));
+    if (n_seg)
+        launch_spmm_quant_bf16(
+            s, out_f32, indices.data_ptr<int32_t>(),
+            reinterpret_cast<const ushort*>(xl.data_ptr()), q_payload, q_desc,
+            y.data_ptr(),
+            src_scale.numel() ? src_scale.data_ptr<float>() : nullptr,
+            dst_scale.numel() ? dst_scale.data_ptr<float>() : nullptr,
+            seg_row.data_ptr<int32_t>(), seg_e0.data_ptr<int32_t>(),
+            seg_e1.data_ptr<int32_t>(), seg_part.data_ptr<int32_t>(),
+            part.data_ptr<float>(), ad_ptr, n_seg, F, n_local);
+    if (zero_rows.numel()) {
+        const dim3 zb(256), zg((zero_rows.numel() + 3) / 4);
+        if (out_f32)
+            combine_parts_kernel<float><<<zg, zb, 0, s>>>(
+                y.data_ptr<float>(), part.data_ptr<float>(),
+                zero_rows.data_ptr<int32_t>(), part_ptr.data_ptr<int32_t>(),
+                reinterpret_cast<const float*>(ad_ptr), zero_rows.numel(), F);
+        else
+            combine_parts_kernel<ushort><<<zg, zb, 0, s>>>(
+                reinterpret_cast<ushort*>(y.data_ptr()),
+                part.data_ptr<float>(), zero_rows.data_ptr<int32_t>(),
+                part_ptr.data_ptr<int32_t>(),
+                reinterpret_cast<const ushort*>(ad_ptr), zero_rows.numel(), F);
+    }
+}
+
 // Row-skipping spmm_csr (spmm_rowskip.hip), fp32 only: `live` is row_live(xl)
 // (uint8 [n_local], 1 = the row holds a non-zero); local columns whose flag is
 // 0 are not fetched. Same bits as spmm_csr on the same operands.
@@ -1371,6 +1485,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "spmm_csr gathering bf16 rows into fp32 accumulators, addend and "
           "output (CDNA4)",
           pybind11::arg("indices"), pybind11::arg("xl"), pybind11::arg("xr"),
+          pybind11::arg("y"), pybind11::arg("src_scale"),
+          pybind11::arg("dst_scale"), pybind11::arg("seg_row"),
+          pybind11::arg("seg_e0"), pybind11::arg("seg_e1"),
+          pybind11::arg("seg_part"), pybind11::arg("zero_rows"),
+          pybind11::arg("part_ptr"), pybind11::arg("n_part"),
+          pybind11::arg("addend"));
+    m.def("spmm_csr_quant_bf16", &spmm_csr_quant_bf16,
+          "spmm_csr on bf16 rows gathering remote columns from the quantized "
+          "wire payload, bf16 or fp32 output (CDNA4)",
+          pybind11::arg("indices"), pybind11::arg("xl"),
+          pybind11::arg("q_payload"), pybind11::arg("q_desc"),
           pybind11::arg("y"), pybind11::arg("src_scale"),
           pybind11::arg("dst_scale"), pybind11::arg("seg_row"),
           pybind11::arg("seg_e0"), pybind11::arg("seg_e1"),

@@ -27,8 +27,8 @@ from torch import Tensor
 from ..helpers import BitType, DistGNNType, PropagationMode
 from ..comm.communicator import Communicator
 from .kernels import (mixed_quantize, mixed_dequantize, spmm, QuantRemote,
-                      resolve_fused_dequant, resolve_bwd_gather_bf16,
-                      round_rows_bf16)
+                      resolve_fused_dequant, resolve_fused_dequant_bf16,
+                      resolve_bwd_gather_bf16, round_rows_bf16)
 
 
 # --------------------------------------------------------------------------
@@ -59,10 +59,19 @@ def _exchange_start(engine, x_local: Tensor, key: str, quant: bool):
 def _fused_dequant(engine, x_local: Tensor, key: str, quant: bool) -> bool:
     """True if this exchange hands the SpMM the wire buffer instead of a
     dequantized block: the engine's switch is on, the exchange is
-    quantized, fp32, on the GPU, and the plan has its per-row table."""
-    return (quant and x_local.is_cuda and x_local.dtype == torch.float32
+    quantized, fp32, on the GPU, and the plan has its per-row table. A bf16
+    exchange qualifies too when ``engine.fused_dequant_bf16`` is on as well
+    (the SpMM then runs csrc/spmm_quant_bf16.hip)."""
+    return (quant and x_local.is_cuda
+            and (x_local.dtype == torch.float32
+                 or (x_local.dtype == torch.bfloat16 and _quant_bf16(engine)))
             and resolve_fused_dequant(getattr(engine, 'fused_dequant', None))
             and engine.plans[key].recv.row_tab is not None)
+
+
+def _quant_bf16(engine) -> bool:
+    return resolve_fused_dequant_bf16(
+        getattr(engine, 'fused_dequant_bf16', None))
 
 
 def _exchange_finish(engine, staged, key: str, fused: bool = False,
@@ -152,11 +161,17 @@ def _agg(engine, view, x_local: Tensor, x_remote, src_scale, dst_scale,
     the same handle serves every view). ``out_dtype``: the mixed call, bf16
     rows gathered into an fp32 result. ``live``: ``row_live(x_local)``, one
     array of the local rows for every view; all-zero local rows are not
-    fetched."""
+    fetched. A QuantRemote ``x_remote`` goes to spmm with the engine's
+    ``fused_dequant_bf16`` switch as ``quant_bf16`` (only bf16 rows read it;
+    ``packed`` and ``live`` are then dropped for that view)."""
     ds = (dst_scale[view.base:view.base + view.nrows]
           if dst_scale is not None else None)
     ad = (addend[view.base:view.base + view.nrows]
           if addend is not None else None)
+    if isinstance(x_remote, QuantRemote) and x_local.dtype == torch.bfloat16:
+        return spmm(view, x_local, x_remote, src_scale, ds, out=out,
+                    addend=ad, packed=packed, out_dtype=out_dtype, live=live,
+                    quant_bf16=_quant_bf16(engine))
     if out_dtype is not None:
         assert packed is None
         return spmm(view, x_local, x_remote, src_scale, ds, out=out,

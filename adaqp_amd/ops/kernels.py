@@ -136,6 +136,12 @@ SPMM_CHUNK = int(_os.environ.get('ADAQP_SPMM_CHUNK', '4'))
 # has. Same bits either way. ADAQP_SPMM_COMPACT=1 turns it on (read once,
 # here); profiles/spmm_compact_NOTES.md has the measurement.
 SPMM_COMPACT = _os.environ.get('ADAQP_SPMM_COMPACT', '0') == '1'
+# what spmm does with a QuantRemote whose gathered rows are bf16 (a bf16 call,
+# or the mixed call with out_dtype=torch.float32): False = dequantize it into
+# a bf16 block, True = gather from the wire (csrc/spmm_quant_bf16.hip). Same
+# bits either way. ADAQP_FUSED_DEQUANT_BF16=1 turns it on (read once, here);
+# profiles/spmm_quant_bf16_NOTES.md has the measurement.
+QUANT_BF16 = _os.environ.get('ADAQP_FUSED_DEQUANT_BF16', '0') == '1'
 
 
 def _auto_seg(num_edges: int, num_rows: int) -> int:
@@ -336,6 +342,15 @@ def resolve_fused_dequant(flag: Optional[bool]) -> bool:
     return bool(flag)
 
 
+def resolve_fused_dequant_bf16(flag: Optional[bool]) -> bool:
+    """``None`` -> on iff env ``ADAQP_FUSED_DEQUANT_BF16=1``; an explicit bool
+    wins. (``GraphEngine.fused_dequant_bf16`` is the flag; ops/dist_agg.py
+    resolves it at every propagation.)"""
+    if flag is None:
+        return _os.environ.get('ADAQP_FUSED_DEQUANT_BF16') == '1'
+    return bool(flag)
+
+
 def resolve_bwd_gather_bf16(flag: Optional[bool]) -> bool:
     """``None`` -> on iff env ``ADAQP_BWD_GATHER_BF16=1``; an explicit bool
     wins. (``GraphEngine.bwd_gather_bf16`` is the flag; the two backward
@@ -422,6 +437,9 @@ class QuantRemote:
     plan does not cover reads as zero instead of being left unwritten.
     ``rows``: rows of the remote block (default: the plan's table).
 
+    With bf16 local rows and ``spmm(..., quant_bf16=True)`` the bf16 gather
+    (csrc/spmm_quant_bf16.hip) does the same against a bf16 block.
+
     The gather's loads reach up to QUANT_PAD bytes past the wire length,
     so on the GPU the payload has to start 4-byte aligned and have that
     many spare bytes behind it in its storage (``wire_buffer`` allocates
@@ -464,6 +482,16 @@ class QuantRemote:
                 and self.plan.row_tab is not None
                 and x_local.shape[0] > 0 and self.rows > 0)
 
+    def fusable_bf16(self, x_local: Tensor) -> bool:
+        """True if :func:`spmm` with ``quant_bf16`` on runs the bf16
+        quantized-gather kernel for this operand: GPU, bf16, even F, a
+        per-row table in the plan, and at least one local and one remote
+        row. Everything else dequantizes."""
+        return (x_local.is_cuda and x_local.dtype == torch.bfloat16
+                and x_local.dim() == 2 and x_local.shape[1] % 2 == 0
+                and self.plan.row_tab is not None
+                and x_local.shape[0] > 0 and self.rows > 0)
+
     def descriptors(self) -> Tensor:
         """int32 [rows, 4] {payload byte offset, bits, inv, rmin} per
         remote row, built once on the current stream."""
@@ -493,7 +521,8 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
          live: Optional[Tensor] = None,
          order: Optional[int] = None,
          chunk: Optional[int] = None,
-         compact: Optional[bool] = None) -> Tensor:
+         compact: Optional[bool] = None,
+         quant_bf16: Optional[bool] = None) -> Tensor:
     """Aggregation SpMM over an in-edge CSR view.
 
     Columns < len(x_local) read x_local; the rest read x_remote (the
@@ -520,8 +549,9 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     bf16 it is the dense remote operand of a packed call.
     ``out_dtype=torch.float32`` with a bf16 ``x_local`` is the mixed call
     (csrc/spmm_mixed.hip): ``x_remote`` is bf16 (or None, or a QuantRemote,
-    which is dequantized into a bf16 block), ``out`` and ``addend`` are
-    fp32 and ``packed`` must be None. The rows are only gathered in bf16;
+    which is dequantized into a bf16 block unless ``quant_bf16`` is on),
+    ``out`` and ``addend`` are fp32 and ``packed`` must be None. The rows
+    are only gathered in bf16;
     the result equals ``spmm`` on the widened operands bit for bit.
     ``live``: ``row_live(x_local)`` (GPU, fp32 or bf16 with even F); local
     rows it marks as all zero are not fetched, same result bit for bit. A 0
@@ -536,6 +566,13 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     ballot per chunk and spends its row fetches on them alone. A bf16 call
     with ``live`` always runs the compacting kernel. Same result bit for bit.
     Without ``live``, and on the CPU, it is ignored.
+    ``quant_bf16``: what happens to a :class:`QuantRemote` whose gathered
+    rows are bf16 (None = QUANT_BF16, off unless ADAQP_FUSED_DEQUANT_BF16=1).
+    On, and with a ``QuantRemote.fusable_bf16`` operand, a bf16 call and the
+    mixed call gather remote columns from the wire
+    (csrc/spmm_quant_bf16.hip) instead of dequantizing it: same result bit
+    for bit. ``packed`` and ``live`` are dropped for such a call, as the fp32
+    quantized gather drops them. It runs the static order.
     ``order`` / ``chunk``: how the GPU kernel hands out segments (None =
     SPMM_ORDER / SPMM_CHUNK): 0 the static order, 1 the ordered sweep in
     tickets of ``chunk`` segments. Same result bit for bit. The mixed,
@@ -545,10 +582,14 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
         'live is not combined with packed or out_dtype'
     if out_dtype is not None:
         return _spmm_mixed(view, x_local, x_remote, src_scale, dst_scale,
-                           out, addend, packed, out_dtype)
+                           out, addend, packed, out_dtype, quant_bf16)
     indptr, indices, num_rows = view.indptr, view.indices, view.nrows
     quant = None
     if isinstance(x_remote, QuantRemote):
+        if (bool(QUANT_BF16 if quant_bf16 is None else quant_bf16)
+                and x_remote.fusable_bf16(x_local)):
+            return _spmm_quant_bf16(view, x_local, x_remote, src_scale,
+                                    dst_scale, out, addend, torch.bfloat16)
         if x_remote.fusable(x_local):
             assert x_remote.F == x_local.shape[1]
             assert view.max_col < x_local.shape[0] + x_remote.rows, \
@@ -637,14 +678,45 @@ def spmm(view: 'SpmmView', x_local: Tensor, x_remote,
     return y
 
 
+def _spmm_quant_bf16(view: 'SpmmView', x_local: Tensor, quant: QuantRemote,
+                     src_scale, dst_scale, out, addend, out_dtype) -> Tensor:
+    """:func:`spmm` on bf16 rows with a ``fusable_bf16`` QuantRemote: remote
+    columns come from the wire, ``out`` and ``addend`` are ``out_dtype``
+    (bf16, or fp32 for the mixed call)."""
+    num_rows, F = view.nrows, x_local.shape[1]
+    assert quant.F == F
+    assert view.max_col < x_local.shape[0] + quant.rows, \
+        'the view names a column past the remote rows described'
+    if out is None:
+        out = torch.empty(num_rows, F, dtype=out_dtype, device=x_local.device)
+    else:
+        assert (out.is_contiguous() and out.shape == (num_rows, F)
+                and out.dtype == out_dtype)
+    assert addend is None or (addend.is_contiguous() and addend.dtype == out_dtype
+                              and addend.shape == out.shape)
+    empty = torch.empty(0, device=x_local.device)
+    native().spmm_csr_quant_bf16(
+        view.indices, x_local.contiguous(), quant.payload, quant.descriptors(),
+        out, src_scale if src_scale is not None else empty,
+        dst_scale if dst_scale is not None else empty,
+        view.seg_row, view.seg_e0, view.seg_e1, view.seg_part, view.zero_rows,
+        view.part_ptr, view.n_part, addend if addend is not None else empty)
+    return out
+
+
 def _spmm_mixed(view: 'SpmmView', x_local: Tensor, x_remote, src_scale,
-                dst_scale, out, addend, packed, out_dtype) -> Tensor:
+                dst_scale, out, addend, packed, out_dtype,
+                quant_bf16=None) -> Tensor:
     """:func:`spmm` with ``out_dtype``: bf16 rows in, fp32 out."""
     assert out_dtype == torch.float32 and x_local.dtype == torch.bfloat16, \
         'the mixed spmm gathers bf16 rows into an fp32 result'
     assert packed is None, 'the mixed spmm takes no packed operand'
     assert x_local.shape[1] % 2 == 0, 'the mixed spmm needs an even F'
     if isinstance(x_remote, QuantRemote):
+        if (bool(QUANT_BF16 if quant_bf16 is None else quant_bf16)
+                and x_remote.fusable_bf16(x_local)):
+            return _spmm_quant_bf16(view, x_local, x_remote, src_scale,
+                                    dst_scale, out, addend, torch.float32)
         x_remote = x_remote.dequantize(torch.bfloat16)
     if x_remote is not None and not x_remote.numel():
         x_remote = None

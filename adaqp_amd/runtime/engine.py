@@ -53,6 +53,11 @@ class GraphEngine:
         # dequantized block (GPU fp32; ops/dist_agg.py). None: on iff env
         # ADAQP_FUSED_DEQUANT=1, read at each propagation; a bool wins.
         self.fused_dequant: Optional[bool] = None
+        # with fused_dequant on, bf16 exchanges do so too and every SpMM
+        # whose gathered rows are bf16 reads the wire buffer
+        # (csrc/spmm_quant_bf16.hip). None: on iff env
+        # ADAQP_FUSED_DEQUANT_BF16=1, read at each propagation; a bool wins.
+        self.fused_dequant_bf16: Optional[bool] = None
         # fp32 backward aggregations gather stochastically rounded bf16 rows
         # (ops/dist_agg.py). None: on iff env ADAQP_BWD_GATHER_BF16=1, read at
         # each backward; a bool wins. The rounding seeds come from a counter

@@ -61,6 +61,8 @@ class Trainer:
             rt['fused_loss'] = True
         if getattr(args, 'fused_dequant', False):
             rt['fused_dequant'] = True
+        if getattr(args, 'fused_dequant_bf16', False):
+            rt['fused_dequant_bf16'] = True
         if getattr(args, 'bwd_gather_bf16', False):
             rt['bwd_gather_bf16'] = True
         self.mode = RunMode(args.mode)
@@ -143,6 +145,8 @@ class Trainer:
                                   msg_dims, agg_type=m['aggregator_type'],
                                   device=self.comm.device)
         self.engine.fused_dequant = self.cfg['runtime'].get('fused_dequant')
+        self.engine.fused_dequant_bf16 = self.cfg['runtime'].get(
+            'fused_dequant_bf16')
         self.engine.bwd_gather_bf16 = self.cfg['runtime'].get('bwd_gather_bf16')
         if getattr(self.args, 'time_breakdown', False):
             self.engine.timer.enabled = True

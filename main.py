@@ -63,6 +63,12 @@ def build_parser() -> argparse.ArgumentParser:
                         'buffer, GPU fp32 (sets runtime.fused_dequant; '
                         'ADAQP_FUSED_DEQUANT=1 is the env switch when neither '
                         'sets it)')
+    p.add_argument('--fused_dequant_bf16', action='store_true',
+                   help='with fused_dequant on, SpMMs that gather bf16 rows '
+                        '(--dtype bf16, or --bwd_gather_bf16) read the wire '
+                        'buffer too (sets runtime.fused_dequant_bf16; '
+                        'ADAQP_FUSED_DEQUANT_BF16=1 is the env switch when '
+                        'neither sets it)')
     p.add_argument('--bwd_gather_bf16', action='store_true',
                    help='fp32 backward SpMMs gather rows rounded to bf16 '
                         'without bias (sets runtime.bwd_gather_bf16; '

@@ -26,6 +26,7 @@ setup(
                      'adaqp_amd/csrc/spmm_packed.hip',
                      'adaqp_amd/csrc/spmm_packed_bf16.hip',
                      'adaqp_amd/csrc/spmm_quant.hip',
+                     'adaqp_amd/csrc/spmm_quant_bf16.hip',
                      'adaqp_amd/csrc/spmm_mixed.hip',
                      'adaqp_amd/csrc/spmm_rowskip.hip',
                      'adaqp_amd/csrc/spmm_compact.hip',

@@ -4,14 +4,20 @@
 A marginal-like view is built on the GPU: ``--rows`` destination rows of
 mean degree ``--deg`` over ``--local`` local and ``--remote`` remote columns,
 each edge remote with probability ``--remote-frac``. The remote block is
-quantized at a uniform bit width. Per width, two pipelines are alternated
-call by call on the same wire bytes and timed with device events:
+quantized at a uniform bit width (``--bits mixed``: 2, 4 or 8 bits per row at
+random). Per width, two pipelines are alternated call by call on the same wire
+bytes and timed with device events:
 
   unfused: quant_unpack (mixed_dequantize into a fresh [R, F] block) + the
            dense SpMM
   fused:   the row-descriptor kernel + the quantized-gather SpMM
 
-after checking that both give the same bits. Reported as median (min..max)."""
+after checking that both give the same bits. Reported as median (min..max).
+
+``--dtype bf16`` gathers bf16 rows: the unfused pipeline unpacks into a bf16
+block and runs the dense bf16 SpMM, or with ``--out-dtype fp32`` the mixed
+SpMM (bf16 rows, fp32 result); the fused one is the bf16 quantized-gather
+kernel (``spmm(..., quant_bf16=True)``) with the same output type."""
 import argparse
 import os
 import statistics
@@ -49,7 +55,18 @@ def main():
     p.add_argument('--density', type=float, default=1.0,
                    help='< 1: zero local elements i.i.d. and also time the '
                         'unfused pipeline with the packed local gather')
+    p.add_argument('--dtype', choices=['fp32', 'bf16'], default='fp32',
+                   help='dtype of the gathered rows')
+    p.add_argument('--out-dtype', choices=['same', 'fp32'], default='same',
+                   help='fp32 with --dtype bf16: the mixed SpMM')
     args = p.parse_args()
+    bf16 = args.dtype == 'bf16'
+    assert bf16 or args.out_dtype == 'same', '--out-dtype fp32 needs --dtype bf16'
+    assert not bf16 or args.density == 1.0, '--density is for fp32'
+    dt = torch.bfloat16 if bf16 else torch.float32
+    # keywords of the SpMM under test and of its unfused counterpart
+    okw = {'out_dtype': torch.float32} if args.out_dtype == 'fp32' else {}
+    qkw = dict(okw, quant_bf16=True) if bf16 else {}
     assert torch.cuda.is_available()
     from adaqp_amd.comm.buffers import _layout
     from adaqp_amd.ops.kernels import (QuantRemote, SpmmView, mixed_dequantize,
@@ -68,7 +85,7 @@ def main():
     rem_c = (r * R // args.rows + (jit * R * 0.01).long()).clamp_(0, R - 1) + NL
     indices = torch.where(rem, rem_c, loc_c)
     view = SpmmView(indptr.to(dev), indices.to(dev), 0, args.rows).to(dev)
-    xl = torch.randn(NL, F, device=dev)
+    xl = torch.randn(NL, F, device=dev).to(dt)
     pk = None
     if args.density < 1.0:      # what the fused path gives up: packed local rows
         xl *= torch.rand(NL, F, device=dev) < args.density
@@ -77,24 +94,28 @@ def main():
     dst = torch.rand(args.rows, device=dev) + 0.5
     rows = torch.arange(R)
     print(f'rows={args.rows} E={E} local={NL} remote={R} F={F} remote edges '
-          f'{float(rem.float().mean()):.3f}; [R, F] fp32 block not allocated '
-          f'by the fused path: {R * F * 4 / 2**20:.1f} MiB')
-    for bits in [int(b) for b in args.bits.split(',')]:
-        plan = _layout([torch.full((R,), bits)], [rows], F).to(dev)
+          f'{float(rem.float().mean()):.3f}; [R, F] {args.dtype} block not '
+          f'allocated by the fused path: '
+          f'{R * F * xl.element_size() / 2**20:.1f} MiB')
+    for bits in args.bits.split(','):
+        row_bits = (torch.tensor([2, 4, 8])[torch.randint(0, 3, (R,), generator=gen)]
+                    if bits == 'mixed' else torch.full((R,), int(bits)))
+        plan = _layout([row_bits], [rows], F).to(dev)
         payload, params = mixed_quantize(xsrc, plan, 11)
         buf = QuantRemote.wire_buffer(plan.total_bytes, dev).copy_(payload)
 
         def unfused():
             xr = mixed_dequantize(buf, params, plan,
-                                  torch.empty(R, F, device=dev))
-            return spmm(view, xl, xr, None, dst)
+                                  torch.empty(R, F, dtype=dt, device=dev))
+            return spmm(view, xl, xr, None, dst, **okw)
 
         def fused():
-            return spmm(view, xl, QuantRemote(buf, params, plan, F), None, dst)
+            return spmm(view, xl, QuantRemote(buf, params, plan, F), None, dst,
+                        **qkw)
 
         def dequant_only():
             return mixed_dequantize(buf, params, plan,
-                                    torch.empty(R, F, device=dev))
+                                    torch.empty(R, F, dtype=dt, device=dev))
 
         def desc_only():
             return QuantRemote(buf, params, plan, F).descriptors()
@@ -114,7 +135,7 @@ def main():
         torch.cuda.synchronize()
         a, b = list(outs.values())[:2]
         print(f'bits={bits} wire {plan.total_bytes / 2**20:.1f} MiB: outputs '
-              f'bit-identical: {torch.equal(a.view(torch.int32), b.view(torch.int32))}')
+              f'bit-identical: {a.dtype == b.dtype and torch.equal(a.view(torch.uint8), b.view(torch.uint8))}')
         del outs, a, b
         times = {k: [] for k in fns}
         for _ in range(args.iters):
