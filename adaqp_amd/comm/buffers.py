@@ -55,6 +55,16 @@ class SidePlan:
     # row r, all zero (bits 0) for a row no peer sends. None when it was not
     # asked for or total_bytes does not fit an unsigned 32-bit offset.
     row_tab: Optional[Tensor] = None
+    # send side: send_rows int64 [S] = the peers' send rows concatenated, so
+    # indexed by send slot (the position in graph.total_send_idx); send_tab
+    # int32 [S, 4], row s = {source row in x_local, wire byte offset (the
+    # unsigned 32-bit value's bits), params slot (= RNG tag), bits} of send
+    # slot s: the one-launch quantizer's descriptor (csrc/quant_mixed.hip).
+    # Both None when not asked for; send_tab also None when total_bytes does
+    # not fit an unsigned 32-bit offset or a source row does not fit int32.
+    send_rows: Optional[Tensor] = None
+    send_tab: Optional[Tensor] = None
+    send_max_row: int = -1        # largest source row (-1: none), host side
 
     @property
     def param_splits(self) -> List[int]:
@@ -66,6 +76,10 @@ class SidePlan:
         self.off = {b: t.to(device) for b, t in self.off.items()}
         if self.row_tab is not None:
             self.row_tab = self.row_tab.to(device)
+        if self.send_rows is not None:
+            self.send_rows = self.send_rows.to(device)
+        if self.send_tab is not None:
+            self.send_tab = self.send_tab.to(device)
         return self
 
 
@@ -98,15 +112,38 @@ def _row_table(rows: Dict[int, Tensor], pos: Dict[int, Tensor],
     return tab.to(torch.int32)
 
 
+def _send_table(slot: Dict[int, Tensor], rows: Dict[int, Tensor],
+                pos: Dict[int, Tensor], off: Dict[int, Tensor],
+                total_nodes: int, total_bytes: int,
+                max_row: int) -> Optional[Tensor]:
+    """The per-send-slot view of a send layout (SidePlan.send_tab): the same
+    rows/pos/off, indexed by send slot instead of grouped by bit width."""
+    if total_bytes >= 2 ** 32 or max_row >= 2 ** 31:
+        return None
+    tab = torch.zeros(total_nodes, 4, dtype=torch.int64)
+    for b in BITS_SET:
+        tab[slot[b], 0] = rows[b]
+        tab[slot[b], 1] = off[b]
+        tab[slot[b], 2] = pos[b]
+        tab[slot[b], 3] = b
+    tab[:, 1] -= (tab[:, 1] >= 2 ** 31).to(torch.int64) * 2 ** 32
+    return tab.to(torch.int32)
+
+
 def _layout(bits_per_peer: List[Optional[Tensor]],
             rows_per_peer: List[Optional[Tensor]], F: int,
-            row_tab: bool = True) -> SidePlan:
+            row_tab: bool = True, send_tab: bool = False) -> SidePlan:
     """Build one side's layout from per-peer bit vectors (agreed order).
     ``row_tab``: also build the per-row table (the recv side's rows are
-    remote-block rows, each at most once; a send side has no use for it)."""
+    remote-block rows, each at most once; a send side has no use for it).
+    ``send_tab``: also build the send side's per-slot table and row list
+    (a source row may be sent to several peers, so it is indexed by send
+    slot, not by row)."""
     rows = {b: [] for b in BITS_SET}
     pos = {b: [] for b in BITS_SET}
     off = {b: [] for b in BITS_SET}
+    slot = {b: [] for b in BITS_SET}
+    slot_rows: List[Tensor] = []
     byte_splits, node_splits = [], []
     p_cursor = 0
     b_cursor = 0
@@ -117,6 +154,7 @@ def _layout(bits_per_peer: List[Optional[Tensor]],
             node_splits.append(0)
             continue
         peer_bytes = 0
+        slot_rows.append(rows_vec.to(torch.int64))
         for b in BITS_SET:
             sel = torch.nonzero(bits_vec == b, as_tuple=True)[0]
             k = int(sel.numel())
@@ -124,6 +162,7 @@ def _layout(bits_per_peer: List[Optional[Tensor]],
                 continue
             bpn = bytes_per_node(F, b)
             rows[b].append(rows_vec[sel])
+            slot[b].append(sel + sum(node_splits))
             pos[b].append(torch.arange(k, dtype=torch.int64) + p_cursor)
             off[b].append(torch.arange(k, dtype=torch.int64) * bpn + b_cursor)
             p_cursor += k
@@ -138,8 +177,17 @@ def _layout(bits_per_peer: List[Optional[Tensor]],
                      for b, v in d.items()}
     rows, pos, off = cat(rows), cat(pos), cat(off)
     tab = _row_table(rows, pos, off, b_cursor) if row_tab else None
-    return SidePlan(F, rows, pos, off, byte_splits, node_splits,
+    plan = SidePlan(F, rows, pos, off, byte_splits, node_splits,
                     b_cursor, p_cursor, tab)
+    if send_tab:
+        plan.send_rows = (torch.cat(slot_rows) if slot_rows
+                          else torch.empty(0, dtype=torch.int64))
+        assert plan.send_rows.numel() == p_cursor
+        plan.send_max_row = (int(plan.send_rows.max()) if p_cursor else -1)
+        assert p_cursor == 0 or int(plan.send_rows.min()) >= 0
+        plan.send_tab = _send_table(cat(slot), rows, pos, off, p_cursor,
+                                    b_cursor, plan.send_max_row)
+    return plan
 
 
 def exchange_bits(comm: Communicator, graph: LocalGraph,
@@ -178,8 +226,14 @@ def build_key_plan(comm: Communicator, graph: LocalGraph, F: int,
         n = graph.recv_splits[p]
         recv_rows_l.append(torch.arange(base, base + n, dtype=torch.int64) if n else None)
         base += n
-    plan = KeyPlan(F, _layout(send_bits_l, send_rows_l, F, row_tab=False),
+    plan = KeyPlan(F, _layout(send_bits_l, send_rows_l, F, row_tab=False,
+                              send_tab=True),
                    _layout(recv_bits_l, recv_rows_l, F))
+    # send slot s is position s of total_send_idx: the traced accumulator
+    # (GraphEngine.traced) is indexed that way
+    assert torch.equal(plan.send.send_rows,
+                       graph.total_send_idx.cpu().to(torch.int64)), \
+        'send plan rows are not graph.total_send_idx'
     if device is not None:
         plan.to(device)
     return plan

@@ -677,6 +677,12 @@ void launch_spmm_compact(
     const void* addend, int64_t n_seg, int64_t F, int64_t n_local,
     int order, int chunk, int32_t* ticket);
 
+// quant_mixed.hip
+bool quant_mixed_ok(int64_t F);
+void quant_pack_mixed(torch::Tensor x, torch::Tensor send_tab, int64_t seed,
+                      torch::Tensor payload, torch::Tensor params,
+                      torch::Tensor trace);
+
 static inline hipStream_t cur_stream() {
     return at::cuda::getCurrentHIPStream().stream();
 }
@@ -1466,6 +1472,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused minmax+stochastic-quantize+bitpack (CDNA4)");
     m.def("quant_unpack", &quant_unpack,
           "fused dequantize+scatter (CDNA4)");
+    m.def("quant_pack_mixed", &quant_pack_mixed,
+          "one-launch mixed-bit quant_pack over a send-side row table, with "
+          "an optional in-kernel variance trace: same bytes as quant_pack",
+          pybind11::arg("x"), pybind11::arg("send_tab"), pybind11::arg("seed"),
+          pybind11::arg("payload"), pybind11::arg("params"),
+          pybind11::arg("trace"));
+    m.def("quant_mixed_ok", &quant_mixed_ok,
+          "true if quant_pack_mixed serves rows of F features");
     m.def("spmm_csr", &spmm_csr,
           "CSR SpMM with fused degree normalization and an optional "
           "epilogue addend (CDNA4)",

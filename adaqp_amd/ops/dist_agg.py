@@ -26,7 +26,8 @@ from torch import Tensor
 
 from ..helpers import BitType, DistGNNType, PropagationMode
 from ..comm.communicator import Communicator
-from .kernels import (mixed_quantize, mixed_dequantize, spmm, QuantRemote,
+from .kernels import (mixed_quantize, mixed_quantize_fused,
+                      resolve_fused_quant, mixed_dequantize, spmm, QuantRemote,
                       resolve_fused_dequant, resolve_fused_dequant_bf16,
                       resolve_bwd_gather_bf16, round_rows_bf16)
 
@@ -44,6 +45,17 @@ def _exchange_start(engine, x_local: Tensor, key: str, quant: bool):
     if quant:
         plan = engine.plans[key]
         seed = engine.next_seed()
+        if x_local.is_cuda and resolve_fused_quant(
+                getattr(engine, 'fused_quant', None)):
+            # one launch for every bit width; on a tracing epoch the same
+            # launch adds the variance proxy into traced[key], so the
+            # index_select + engine.trace pair is not run
+            acc = (engine.trace_accumulator(key)
+                   if engine.is_tracing and engine.graph.num_send else None)
+            with engine.timer.record(f'{key}_quant'):
+                payload, params = mixed_quantize_fused(x_local, plan.send,
+                                                       seed, trace=acc)
+            return ('qt', payload, params, x_local.dtype)
         if engine.is_tracing:
             send = x_local.index_select(0, engine.graph.total_send_idx)
             engine.trace(key, send)

@@ -76,6 +76,71 @@ def mixed_quantize(x: Tensor, plan: SidePlan, seed: int) -> Tuple[Tensor, Tensor
     return payload, params
 
 
+def trace_rows(send: Tensor) -> Tensor:
+    """fp32 [S]: the quantization-variance proxy (F/6) * (rmax - rmin)^2 of
+    each row of ``send`` [S, F] (``GraphEngine.trace`` accumulates it): the
+    range is subtracted in send's dtype, squared and scaled in fp32."""
+    rng = send.max(dim=1).values - send.min(dim=1).values
+    return (send.shape[1] / 6.0) * rng.float() ** 2
+
+
+def quant_mixed_fast(x: Tensor, plan: SidePlan) -> bool:
+    """True if :func:`mixed_quantize_fused` runs the one-launch kernel
+    (csrc/quant_mixed.hip) for this input: a GPU, contiguous fp32 or bf16
+    [N, F] tensor with F % 4 == 0, F <= 1024 and rows aligned to the kernel's
+    4-feature loads, and a send-slot table in the plan. Everything else takes
+    the per-bit path."""
+    return (x.is_cuda and x.dim() == 2 and x.is_contiguous()
+            and x.dtype in (torch.float32, torch.bfloat16)
+            and native().quant_mixed_ok(x.shape[1])
+            and x.data_ptr() % (4 * x.element_size()) == 0
+            and plan.send_tab is not None and plan.send_tab.is_cuda)
+
+
+def mixed_quantize_fused(x: Tensor, plan: SidePlan, seed: int,
+                         trace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """:func:`mixed_quantize` in one launch for every bit width, same
+    (payload, params) bit for bit; no launch for an empty send set.
+    ``trace``: fp32 [S] accumulator indexed by send slot (the plan must have
+    been built with its send-slot rows); ``trace[s] += trace_rows(x[send
+    rows])[s]``, computed in the same kernel. Inputs that do not qualify
+    (:func:`quant_mixed_fast`) run :func:`mixed_quantize` and, with ``trace``,
+    the torch formula."""
+    assert plan.F == x.shape[1]
+    if trace is not None:
+        assert plan.send_rows is not None, \
+            'the plan was built without its send-slot rows'
+        assert (trace.dtype == torch.float32 and trace.is_contiguous()
+                and trace.shape == (plan.total_nodes,)
+                and trace.device == x.device)
+    if not quant_mixed_fast(x, plan):
+        if trace is not None and plan.total_nodes:
+            with torch.no_grad():
+                trace += trace_rows(x.index_select(0, plan.send_rows))
+        return mixed_quantize(x, plan, seed)
+    payload = torch.empty(plan.total_bytes, dtype=torch.uint8, device=x.device)
+    params = torch.empty(2 * plan.total_nodes, dtype=torch.bfloat16,
+                         device=x.device)
+    if plan.total_nodes:
+        assert (plan.send_tab.shape[0] == plan.total_nodes
+                and plan.send_max_row < x.shape[0]), \
+            'the send plan names a row past x'
+        native().quant_pack_mixed(
+            x, plan.send_tab, int(seed) & Q._M32, payload, params,
+            trace if trace is not None
+            else torch.empty(0, dtype=torch.float32, device=x.device))
+    return payload, params
+
+
+def resolve_fused_quant(flag: Optional[bool]) -> bool:
+    """``None`` -> on iff env ``ADAQP_FUSED_QUANT=1``; an explicit bool wins.
+    (``GraphEngine.fused_quant`` is the flag; ops/dist_agg.py resolves it at
+    every quantized exchange.)"""
+    if flag is None:
+        return _os.environ.get('ADAQP_FUSED_QUANT') == '1'
+    return bool(flag)
+
+
 def mixed_dequantize(payload: Tensor, params: Tensor, plan: SidePlan,
                      out: Tensor) -> Tensor:
     """Unpack wire payload into fp rows of ``out`` (remote block [R, F]),

@@ -58,6 +58,11 @@ class GraphEngine:
         # (csrc/spmm_quant_bf16.hip). None: on iff env
         # ADAQP_FUSED_DEQUANT_BF16=1, read at each propagation; a bool wins.
         self.fused_dequant_bf16: Optional[bool] = None
+        # quantized exchanges pack every bit width in one launch and, on a
+        # tracing epoch, accumulate the variance proxy in that launch
+        # (csrc/quant_mixed.hip; ops/dist_agg.py). Same wire bytes. None: on
+        # iff env ADAQP_FUSED_QUANT=1, read at each exchange; a bool wins.
+        self.fused_quant: Optional[bool] = None
         # fp32 backward aggregations gather stochastically rounded bf16 rows
         # (ops/dist_agg.py). None: on iff env ADAQP_BWD_GATHER_BF16=1, read at
         # each backward; a bool wins. The rounding seeds come from a counter
@@ -172,6 +177,15 @@ class GraphEngine:
                 self.traced[key] += v
             else:
                 self.traced[key] = v.clone()
+
+    def trace_accumulator(self, key: str) -> Tensor:
+        """``traced[key]`` as the fp32 [num_send] accumulator the one-launch
+        quantizer adds into, zero-filled on first use (0 + v == v, so the
+        bits are those ``trace`` would have left)."""
+        if key not in self.traced:
+            self.traced[key] = torch.zeros(
+                self.graph.num_send, dtype=torch.float32, device=self.device)
+        return self.traced[key]
 
     def reset_trace(self) -> None:
         self.traced = {}

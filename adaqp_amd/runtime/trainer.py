@@ -65,6 +65,8 @@ class Trainer:
             rt['fused_dequant_bf16'] = True
         if getattr(args, 'bwd_gather_bf16', False):
             rt['bwd_gather_bf16'] = True
+        if getattr(args, 'fused_quant', False):
+            rt['fused_quant'] = True
         self.mode = RunMode(args.mode)
         self.model_type = MODEL_MAP[args.model_name]
         self.comm = Communicator(backend=getattr(args, 'backend', None),
@@ -148,6 +150,7 @@ class Trainer:
         self.engine.fused_dequant_bf16 = self.cfg['runtime'].get(
             'fused_dequant_bf16')
         self.engine.bwd_gather_bf16 = self.cfg['runtime'].get('bwd_gather_bf16')
+        self.engine.fused_quant = self.cfg['runtime'].get('fused_quant')
         if getattr(self.args, 'time_breakdown', False):
             self.engine.timer.enabled = True
         if getattr(self.args, 'dtype', 'fp32') == 'bf16':

@@ -74,6 +74,11 @@ def build_parser() -> argparse.ArgumentParser:
                         'without bias (sets runtime.bwd_gather_bf16; '
                         'ADAQP_BWD_GATHER_BF16=1 is the env switch when '
                         'neither sets it)')
+    p.add_argument('--fused_quant', action='store_true',
+                   help='quantized exchanges pack every bit width in one '
+                        'launch and trace the variance proxy in it, same wire '
+                        'bytes (sets runtime.fused_quant; ADAQP_FUSED_QUANT=1 '
+                        'is the env switch when neither sets it)')
     return p
 
 

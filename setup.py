@@ -30,7 +30,8 @@ setup(
                      'adaqp_amd/csrc/spmm_mixed.hip',
                      'adaqp_amd/csrc/spmm_rowskip.hip',
                      'adaqp_amd/csrc/spmm_compact.hip',
-                     'adaqp_amd/csrc/masked_loss.hip'],
+                     'adaqp_amd/csrc/masked_loss.hip',
+                     'adaqp_amd/csrc/quant_mixed.hip'],
             extra_compile_args={'cxx': ['-O3'],
                                 'nvcc': ['-O3', '--offload-arch=gfx950']},
         )
